@@ -9,7 +9,24 @@ path has; vortex_amd/shard.py).  Inputs are resident in HBM before the timed
 region.  Weak scaling: every GPU hashes its own 65,536 pieces
 (global index r*65536 + i, BASELINE config 4 at N=8).
 
-Extra fields (DESIGN.md §7 "Measurement"; all but roofline at N=1 only):
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the
+headline needs: it builds the expected table and the batch, warms up, times
+the K steps, checks the last step's verdicts, writes them if --dump-outputs
+is given, and prints the line (headline fields, config, roofline from the
+timed steps' own events and clock stamps, parity).  Every other leg below
+takes runs of its own and is measured only with --full (the --no-* options
+then drop single legs); --reverify-multi stays its own opt-in.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed
+step returned to its caller as float32 DIR/<name>.npy — `matched` (this
+rank's per-piece verdicts, 1.0 = digest equals the expected one) and, under
+torch.distributed, `verdicts` (the gathered table) — at most 64 MB in all (a
+fixed, seeded sample of a larger array).  The inputs depend only on the
+arguments (counter-based generator, fixed seeds), so two builds can be
+compared output for output.
+
+Extra fields (DESIGN.md §7 "Measurement"; all but roofline with --full only,
+and at N=1 only):
   roofline       dominant kernel's achieved algorithmic bytes per launch / its
                  HIP-event duration on the launch stream, vs 8 TB/s HBM3E
                  (the metric's fraction); traffic = corrected PMC FETCH bytes
@@ -32,10 +49,11 @@ Extra fields (DESIGN.md §7 "Measurement"; all but roofline at N=1 only):
   reverify_cold  the same with the file's pages evicted before every call
                  (fsync + POSIX_FADV_DONTNEED): reads from the disk.
 At N > 1 (every rank takes part):
-  ranks          every rank's step / kernel / verdict-gather time, shader
-                 clock, and identity (device index, PCI bus id, UUID, the
-                 world size RCCL reported); distinct_devices must hold unless
-                 --same-device (a rehearsal).
+  ranks          every rank's step / kernel time, shader clock, and identity
+                 (device index, PCI bus id, UUID, the world size RCCL
+                 reported); distinct_devices must hold unless --same-device
+                 (a rehearsal).  With --full also verdict_gather_ms: the
+                 verdict all-gather alone, K more times after the timed steps.
   reverify_multi (opt-in, --reverify-multi) config 5 split over the N GPUs by
                  piece index, warm and cold, the slowest rank's time, beside
                  the CPU pool on every node CPU.
@@ -50,7 +68,7 @@ sweep, the nested roofline.valu block, rank identities — goes to the side
 file the line names in `detail` (bench_detail.json beside bench.py, or
 --detail PATH).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 N > 1: either launched by the driver as
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 or started plainly, in which case bench.py starts the N ranks itself (a
@@ -1522,6 +1540,29 @@ class ClockStamps:
         return clock_from_stamps(self.buf[0].cpu().numpy(), self.buf[1].cpu().numpy(), self.khz)
 
 
+DUMP_LIMIT = 64 << 20  # bytes: everything --dump-outputs writes
+
+
+def dump_outputs(out_dir: str, arrays: dict, limit: int = DUMP_LIMIT) -> dict:
+    """Write each array of `arrays` as float32 `out_dir`/<name>.npy, at most
+    `limit` bytes of array data in all.  An array over its equal share of the
+    limit is cut to a fixed sample: sorted indices drawn without replacement
+    by a generator seeded with the array's size alone, so two runs with the
+    same arguments keep the same elements.  Returns {name: elements written}."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = limit // 4 // max(1, len(arrays))  # float32 elements per array
+    written = {}
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if a.size > share:
+            a = a[np.sort(np.random.default_rng(a.size).choice(a.size, share, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
+        written[name] = int(a.size)
+    return written
+
+
 def device_identity(local: int) -> dict:
     """Which physical GPU this rank hashed on (PCI bus id, UUID)."""
     from vortex_amd._lib import check, tuning
@@ -1611,10 +1652,15 @@ def main() -> int:
                     help="untimed steps first: the clock climbs for ~50 ms after the generation kernels")
     ap.add_argument("--pieces", type=int, default=65536, help="pieces per GPU")
     ap.add_argument("--piece-len", type=int, default=262144)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (verdicts) as float32 DIR/<name>.npy, <= 64 MB")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the extra legs (cpu_baseline, ragged, e2e*, reverify*; "
+                         "at N>1 the verdict gather alone); a plain run measures the headline only")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-thread seconds for the baseline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
-    ap.add_argument("--no-ragged", action="store_true", help="skip the config-3 leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU pool baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the host-resident legs")
+    ap.add_argument("--no-ragged", action="store_true", help="with --full: skip the config-3 leg")
     ap.add_argument("--no-reverify", action="store_true", help="skip the config-5 legs (N=1 and N>1)")
     ap.add_argument("--reverify-multi-scale", type=float, default=1.0,
                     help="N>1 re-verify leg: fraction of linux-mint's pieces (rehearsals)")
@@ -1631,6 +1677,8 @@ def main() -> int:
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # N ranks or nothing: a plain `bench.py --gpus N` launches its own ranks
     # (before any GPU call); under a launcher, WORLD_SIZE must be N.
@@ -1760,12 +1808,15 @@ def main() -> int:
         # The verdict all-gather alone, after the timed region: what the one
         # collective costs per step (the scaling overhead at N > 1).
         # (wall clock: RCCL runs on its own stream, gloo on the host)
-        torch.cuda.synchronize()
-        g0 = time.perf_counter()
-        for _ in range(args.steps):
-            gather_verdicts(matched, n_total)
-        torch.cuda.synchronize()
-        gather_ms = (time.perf_counter() - g0) / args.steps * 1e3
+        # These are K gathers of their own, so only --full measures them.
+        gather_ms = 0.0
+        if args.full:
+            torch.cuda.synchronize()
+            g0 = time.perf_counter()
+            for _ in range(args.steps):
+                gather_verdicts(matched, n_total)
+            torch.cuda.synchronize()
+            gather_ms = (time.perf_counter() - g0) / args.steps * 1e3
         # every rank's figures (max over ranks is what `value` uses)
         mine = torch.tensor([elapsed, kern_ms, gather_ms, clock.get("GHz_mean") or 0.0], dtype=torch.float64,
                             device=dev if args.dist_backend == "nccl" else "cpu")
@@ -1784,9 +1835,10 @@ def main() -> int:
             return 4
         ranks = {"step_ms": [round(r[0] / args.steps * 1e3, 4) for r in per],
                  "kernel_ms": [round(r[1], 4) for r in per],
-                 "verdict_gather_ms": [round(r[2], 4) for r in per],
                  "clock_GHz": [round(r[3], 4) for r in per],
                  "devices": idents, "distinct_devices": distinct}
+        if args.full:
+            ranks["verdict_gather_ms"] = [round(r[2], 4) for r in per]
 
     # Verdicts: exactly the corrupted pieces mismatch (checked on the gathered
     # table when N > 1, else locally).
@@ -1799,6 +1851,12 @@ def main() -> int:
     parity = {"checked": len(m), "bit_exact": len(m) - len(want_bad), "corrupt_mismatched": len(want_bad),
               "against": "cpu pool restatement (oracle/pool_oracle.cpp, SHA-NI SHA-1 per piece task)",
               "expected_table_threads": exp_threads, "expected_table_s": round(t_exp, 3)}
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: this rank's verdicts, and the gathered table
+        outs = {"matched": (mbuf[(args.steps - 1) % 2] if overlap else matched).cpu().numpy()}
+        if verdicts is not None:
+            outs["verdicts"] = m
+        log("dump-outputs:", args.dump_outputs, dump_outputs(args.dump_outputs, outs))
 
     total_bytes = n_total * plen
     value = total_bytes / elapsed * args.steps / GiB
@@ -1836,7 +1894,7 @@ def main() -> int:
     # the line down with it.  The driver's N>1 runs print only the
     # config-2/4 line; builder runs add --reverify-multi.
     multi = distributed and args.reverify_multi and not args.no_reverify
-    extra = rank == 0 and world == 1
+    extra = args.full and rank == 0 and world == 1
     if multi or extra:
         del data, matched, expected
         torch.cuda.empty_cache()

@@ -8,6 +8,8 @@
   under torch.distributed.run with one rank the process group is RCCL
   ("nccl") at world size 1, so RCCL init and the device-tensor all-gather of
   the verdicts run on hardware.
+* A plain run measures the headline only (extra legs need --full), and
+  --dump-outputs writes the last timed step's verdicts as float32 .npy files.
 """
 import json
 import os
@@ -146,9 +148,16 @@ def test_plain_bench_launches_its_ranks(built, gpu, n, tmp_path):
     piece indices r*1024 + i, the verdicts of all 8 shards gathered and the
     exact 1 % mismatch set checked on the gathered table."""
     side = tmp_path / "detail.json"
-    r = _run(["--gpus", str(n), "--same-device", "--dist-backend", "gloo", "--detail", str(side)] + SMALL,
-             timeout=300)
+    r = _run(["--gpus", str(n), "--same-device", "--dist-backend", "gloo", "--detail", str(side), "--full",
+              "--dump-outputs", str(tmp_path / "out")] + SMALL,
+             timeout=300)  # --full: the verdict gather alone is timed too (verdict_gather_ms)
     assert r.returncode == 0, r.stderr[-3000:]
+    import numpy as np
+
+    # rank 0's own verdicts and the gathered table of the last timed step: every 100th global piece is corrupt
+    want = np.array([0.0 if i % 100 == 99 else 1.0 for i in range(n * 1024)], dtype=np.float32)
+    assert np.array_equal(np.load(tmp_path / "out" / "matched.npy"), want[:1024])
+    assert np.array_equal(np.load(tmp_path / "out" / "verdicts.npy"), want)
     (res,) = _lines(r.stdout)
     _check_line_size(r.stdout)
     assert res["detail"] == str(side)
@@ -170,6 +179,62 @@ def test_plain_bench_launches_its_ranks(built, gpu, n, tmp_path):
     assert res["parity"]["checked"] == n * 1024 and res["config"]["parity_checked"] == n * 1024
     corrupt = sum(1 for i in range(n * 1024) if i % 100 == 99)
     assert res["parity"]["corrupt_mismatched"] == corrupt and res["parity"]["bit_exact"] == n * 1024 - corrupt
+
+
+def test_steps_must_be_positive():
+    """--steps sets the number of timed steps; none is refused before anything runs."""
+    r = _run(["--gpus", "1", "--steps", "0"], timeout=60)
+    assert r.returncode == 2 and not _lines(r.stdout) and "--steps" in r.stderr
+
+
+def test_dump_outputs_writes_float32_within_the_limit(tmp_path):
+    """bench.dump_outputs: every array as float32 <name>.npy; arrays over their
+    share of the byte limit are cut to the same seeded sample on every call."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    small = np.arange(1000, dtype=np.uint8) % 2
+    big = np.arange(5000, dtype=np.int64)
+    for d in ("a", "b"):
+        wrote = bench.dump_outputs(str(tmp_path / d), {"matched": small, "verdicts": big}, limit=16000)
+        assert wrote == {"matched": 1000, "verdicts": 2000}  # 16,000 B = 2 x 2,000 float32
+    a, b = (np.load(tmp_path / d / "verdicts.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape == (2000,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and set(a.tolist()) <= set(range(5000))  # a sorted subset, no repeats
+    m = np.load(tmp_path / "a" / "matched.npy")
+    assert m.dtype == np.float32 and np.array_equal(m, small.astype(np.float32))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 16000 + 2 * 128
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_verdicts(built, gpu, tmp_path):
+    """A plain run (no --full, no --no-* option) times exactly --steps steps and
+    measures no extra leg; --dump-outputs holds the last timed step's verdicts
+    as float32: 0.0 for exactly the corrupted pieces (every 100th), else 1.0."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    side, out = tmp_path / "detail.json", tmp_path / "out"
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--pieces", "1024", "--detail", str(side),
+              "--dump-outputs", str(out)], timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    (res,) = _lines(r.stdout)
+    _check_line_size(r.stdout)
+    full = json.loads(side.read_text())
+    for rec in (res, full):
+        assert not [k for k in bench.LEGS + ("cpu_baseline",) if k in rec], sorted(rec)
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["n_gpus"] == 1 and res["dtype"] == "u32"
+    assert res["ms_per_step"] > 0 and res["higher_is_better"] is True and res["unit"] == "GiB/s"
+    assert res["value"] == pytest.approx(1024 * 262144 / (res["ms_per_step"] * 1e-3) / (1 << 30), rel=1e-2)
+    assert res["roofline"]["kernel_ms"] > 0 and res["parity"]["checked"] == 1024
+    assert os.listdir(out) == ["matched.npy"]
+    m = np.load(out / "matched.npy")
+    assert m.dtype == np.float32 and m.shape == (1024,)
+    assert np.array_equal(m, np.array([0.0 if i % 100 == 99 else 1.0 for i in range(1024)], dtype=np.float32))
 
 
 @pytest.mark.gpu
@@ -206,7 +271,7 @@ def test_bench_rccl_world_size_1(built, gpu, tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr=127.0.0.1", f"--master-port={port}", BENCH, "--gpus", "1"] + SMALL \
-        + ["--detail", str(tmp_path / "detail.json")]
+        + ["--full", "--detail", str(tmp_path / "detail.json")]  # --full: verdict_gather_ms
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     (res,) = _lines(r.stdout)
