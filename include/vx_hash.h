@@ -33,9 +33,12 @@
  *    Separate contexts (e.g. one per torrent) share nothing but the device
  *    and may be driven from different threads concurrently
  *    (tests/test_gpu_parity.py::test_two_contexts_two_threads).
- *  - Device entry points (vx_sha1_device_*) take device pointers and a HIP
- *    stream (hipStream_t passed as void*; NULL = the null stream) and only
- *    enqueue work: they return before the kernel finishes.
+ *  - Device entry points (vx_sha1_device_*, vx_merkle_device_*) take device
+ *    pointers and a HIP stream (hipStream_t passed as void*; NULL = the null
+ *    stream) and only enqueue work: they return before the kernel finishes.
+ *  - BitTorrent v2 (BEP 52) pieces are verified by the vx_merkle_* entries at
+ *    the end of this file: 32-byte SHA-256 merkle roots in place of the
+ *    20-byte digests, everything else as above.
  */
 #ifndef VX_HASH_H
 #define VX_HASH_H
@@ -482,6 +485,72 @@ int vx_sha1_device_ragged_hint(const void* d_base, const uint64_t* d_offsets, co
 /* Host helper: write into order_out the permutation that sorts lens[0..n)
  * by descending length (stable).  Used to build d_order. */
 int vx_sort_order(const uint32_t* lens, uint32_t n, uint32_t* order_out);
+
+/* ---- BitTorrent v2 (BEP 52): SHA-256 merkle piece verification ----------
+ * A piece is a merkle tree over blocks of VX_MERKLE_BLOCK bytes, so it splits
+ * across lanes where a SHA-1 piece is one chain.
+ *   leaf      SHA-256 of one block; the last block of a piece at its real
+ *             length (no zero fill).  A leaf slot wholly beyond the piece's
+ *             bytes is the zero hash: 32 zero bytes, not the hash of anything.
+ *   node      SHA-256(left || right).
+ *   root      of a piece: the binary tree over width = 2^log2w leaf slots.
+ *             Pieces of a file longer than piece_length (the short last one
+ *             included) have width = piece_length / VX_MERKLE_BLOCK and their
+ *             roots are the file's `piece layers`; a file of at most
+ *             piece_length bytes is one piece whose width is its block count
+ *             rounded up to a power of two and whose root is `pieces root`.
+ *             An empty piece's root is the pad hash of its height.
+ *   pad hash  pad(0) = the zero hash, pad(h) = SHA-256(pad(h-1) || pad(h-1)). */
+#define VX_MERKLE_BLOCK 16384
+#define VX_SHA256_LEN 32
+#define VX_MERKLE_MAX_LOG2_WIDTH 17 /* 2^17 leaves: a 2 GiB piece */
+
+/* Device-resident pieces i in [0,n) at d_base + i*stride, each len bytes, the
+ * last one last_len (0 < last_len <= len); every tree has 2^log2_width leaf
+ * slots (len <= VX_MERKLE_BLOCK << log2_width).  d_leaves (required,
+ * (n << log2_width) * 32 bytes) receives every leaf row of every piece, zero
+ * rows included: piece i's rows start at row i << log2_width; it is the leaf
+ * layer a client serves to peers.  d_roots (n * 32 bytes, may be NULL) gets
+ * the roots; with d_expected and d_matched both given, d_matched[i] =
+ * (root == d_expected[32*i..]) (0/1).  d_base and stride are multiples of 16,
+ * stride >= len, log2_width <= VX_MERKLE_MAX_LOG2_WIDTH and n << log2_width
+ * fits 32 bits.  Enqueue-only, like the SHA-1 device entries; n == 0 launches
+ * nothing. */
+int vx_merkle_device_uniform(const void* d_base, uint64_t stride, uint32_t len, uint32_t last_len, uint32_t n,
+                             uint32_t log2_width, void* d_leaves, void* d_roots, const void* d_expected,
+                             void* d_matched, void* stream);
+/* Ragged batch: piece i at d_base + d_offsets[i] (16-byte aligned), d_lens[i]
+ * bytes (0 allowed).  d_log2w (uint8 per piece, may be NULL = log2_width)
+ * gives piece i a tree of 2^d_log2w[i] <= 2^log2_width leaf slots (the single
+ * piece of a short file); its leaf rows still start at row i << log2_width and
+ * all 2^log2_width of them are written.  The device-resident metadata is not
+ * checked here (see above); vortex_amd.device.merkle_ragged checks it. */
+int vx_merkle_device_ragged(const void* d_base, const uint64_t* d_offsets, const uint32_t* d_lens,
+                            const uint8_t* d_log2w, uint32_t n, uint32_t log2_width, void* d_leaves, void* d_roots,
+                            const void* d_expected, void* d_matched, void* stream);
+/* Root of a layer of n hashes (32 bytes each) that stand `height` levels above
+ * the leaves: the layer is padded to the next power of two with pad(height),
+ * each level above with the next pad hash (how a client checks a received
+ * `piece layers` string against `pieces root`).  d_work: 32*n bytes of
+ * scratch; d_layer is not modified.  height <= 64. */
+int vx_merkle_device_root(const void* d_layer, uint32_t n, uint32_t height, void* d_work, void* d_root,
+                          void* stream);
+/* pad(height) into out[32]; host only.  height <= 128. */
+int vx_merkle_pad_hash(uint32_t height, uint8_t* out);
+/* The synchronous host batch of v2 pieces, the counterpart of
+ * vx_verify_batch: piece i is ptrs[i], lens[i] bytes (plain or registered
+ * host memory), verified against expected[32*i..] as a tree of
+ * 2^log2w[i] leaf slots (log2w NULL: piece_length / VX_MERKLE_BLOCK for
+ * every piece).  matched_out[i] = 0/1; roots_out (may be NULL) gets n * 32
+ * bytes.  Pieces go through the context's slots and pinned stages; one slot's
+ * copy overlaps the previous slot's kernels.  piece_length is a power of two,
+ * VX_MERKLE_BLOCK <= piece_length <= max_piece_len, and lens[i] <=
+ * VX_MERKLE_BLOCK << log2w[i] <= piece_length.  VX_EBUSY while async pieces
+ * are pending.  Counts into vx_get_stats (pieces_completed,
+ * pieces_mismatched, bytes_completed, batches). */
+int vx_merkle_verify_batch(vx_ctx* ctx, const uint8_t* const* ptrs, const uint32_t* lens, const uint8_t* log2w,
+                           size_t n, uint32_t piece_length, const uint8_t* expected, uint8_t* matched_out,
+                           uint8_t* roots_out);
 
 #ifdef __cplusplus
 }

@@ -34,6 +34,9 @@ VX_ENODEV = -19
 VX_EDEVICE = -5
 VX_EBUSY = -16
 
+VX_MERKLE_BLOCK = 16384  # BitTorrent v2 (BEP 52) leaf block
+VX_SHA256_LEN = 32
+
 # Every function include/vx_hash.h declares: what libvortex_amd.so exports,
 # and all it exports (tests/test_abi.py checks the headers and both libraries'
 # dynamic symbols against these lists).
@@ -47,6 +50,8 @@ EXPORTS = (
     "vx_last_verify", "vx_last_verify_rounds",
     "vx_split_init", "vx_split_claim", "vx_split_done", "vx_split_boundary", "vx_verify_files_split",
     "vx_verify_files_split_multi",
+    "vx_merkle_device_uniform", "vx_merkle_device_ragged", "vx_merkle_device_root", "vx_merkle_pad_hash",
+    "vx_merkle_verify_batch",
 )
 # ... plus include/vx_tuning.h and include/vx_synth.h: libvortex_amd_tuning.so only.
 TUNING_EXPORTS = (
@@ -182,6 +187,12 @@ def _declare(L: ctypes.CDLL, tuning: bool = False) -> None:
                                    c.c_uint32], c.c_int64),
         "vx_verify_files_split_multi": ([vp, c.c_size_t, vp, vp, c.c_size_t, c.c_uint32, vp, c.c_size_t,
                                          c.POINTER(vx_split), vp, c.c_uint32], c.c_int64),
+        "vx_merkle_device_uniform": ([vp, c.c_uint64, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, vp, vp, vp, vp,
+                                      vp], c.c_int),
+        "vx_merkle_device_ragged": ([vp, vp, vp, vp, c.c_uint32, c.c_uint32, vp, vp, vp, vp, vp], c.c_int),
+        "vx_merkle_device_root": ([vp, c.c_uint32, c.c_uint32, vp, vp, vp], c.c_int),
+        "vx_merkle_pad_hash": ([c.c_uint32, vp], c.c_int),
+        "vx_merkle_verify_batch": ([vp, vp, vp, vp, c.c_size_t, c.c_uint32, vp, vp, vp], c.c_int),
     }
     if tuning:
         sig.update({

@@ -1,0 +1,387 @@
+// sha256_kernels.hip — BitTorrent v2 (BEP 52) piece verification for MI355X
+// (gfx950): SHA-256 merkle trees over 16 KiB blocks.
+//
+// Mapping:
+//  * leaf kernel: one lane per leaf slot.  Lane g serves piece g >> log2_width,
+//    slot g & (width-1); a 16 MiB piece is 1,024 independent lanes where the
+//    SHA-1 kernels have one chain.  A lane streams its block in 128-byte
+//    groups (one L2 line, two SHA-256 blocks) with 8 x global_load_dwordx4,
+//    one group ahead of the compression in a register ring (two groups of
+//    compression, ~2,800 VALU, cover an HBM miss many times over); the loop
+//    bound is wave-uniform, the ring indices compile-time (no scratch).  The
+//    tail of a short leaf is read byte-exactly: no load touches a byte past
+//    the piece's end.  A slot that starts at or past the piece's end gets the
+//    zero hash and hashes nothing.  The padding block of a full leaf is a
+//    compile-time constant (rounds only).
+//  * node kernel: 256 threads reduce a tile of 512 rows in LDS, one node
+//    (two compressions, the second a constant padding block) per thread and
+//    level.  Trees up to 512 leaves share a tile (512 >> log2_width pieces per
+//    workgroup); wider ones take one workgroup per piece, which reduces the
+//    piece tile by tile and then the tiles' tops.  Under 1 % of the leaf work.
+//  * layer kernel (vx_merkle_device_root): the same tile reduction over a
+//    layer of n hashes, missing rows filled with the pad hash of the level.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <string.h>
+
+#include "sha256_device.hpp"
+#include "vx_kernels.h"
+
+namespace vx {
+namespace {
+
+using sha256::State;
+
+constexpr uint32_t kLeaf = 16384;       // VX_MERKLE_BLOCK
+constexpr int kTileLog2 = 9;            // rows a workgroup reduces at once: 512 x 32 B = 16 KiB of LDS
+constexpr uint32_t kTile = 1u << kTileLog2;
+constexpr int kNodeBlock = kTile / 2;   // one thread per node of the tile's first level
+constexpr int kMaxTops = 1 << (kMerkleMaxLog2Width - kTileLog2);
+
+__device__ constexpr sha256::ConstBlock kPadLeaf = sha256::pad_block(kLeaf);  // after a full 16 KiB leaf
+__device__ constexpr sha256::ConstBlock kPadNode = sha256::pad_block(64);     // after left || right
+
+// A line of zeros: the load target for lanes that have no full group to
+// stream, so every issued load stays in bounds.
+__device__ __attribute__((aligned(128))) uint4 g_zero_group[8];
+
+__device__ __forceinline__ void load_group(uint4 (&dst)[8], const uint4* src) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) dst[k] = src[k];
+}
+
+__device__ __forceinline__ void compress_group(State& s, const uint4 (&g)[8]) {
+    sha256::compress_le(s, g[0], g[1], g[2], g[3]);
+    sha256::compress_le(s, g[4], g[5], g[6], g[7]);
+}
+
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t u = __shfl_xor(v, o, 64);
+        v = u > v ? u : v;
+    }
+    return v;
+}
+
+// Stream `ng` 128-byte groups from src with a 2-deep register ring.  ng_wave:
+// the wave-wide loop bound; lanes with ng < ng_wave keep issuing (clamped,
+// in-bounds) loads and skip the compression.
+__device__ __forceinline__ void stream_groups(State& s, const uint4* src, uint32_t ng, uint32_t ng_wave) {
+    if (ng_wave == 0) return;
+    const uint4* base = ng ? src : g_zero_group;
+    const uint32_t last = ng ? ng - 1 : 0;
+    uint4 ring[2][8];
+    load_group(ring[0], base);
+    for (uint32_t g0 = 0; g0 < ng_wave; g0 += 2) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const uint32_t gl_raw = g0 + r + 1;
+            const uint32_t gl = gl_raw < last ? gl_raw : last;
+            load_group(ring[r ^ 1], base + (size_t)gl * 8);
+            if (g0 + r < ng) compress_group(s, ring[r]);
+        }
+    }
+}
+
+// The last rem (< 128) bytes at q (16-byte aligned) of a message of total
+// bytes, then the FIPS 180-4 padding: 1 to 3 blocks, built word by word from
+// bytes inside [q, q+rem) only.  One compression in a loop: this runs once
+// per short leaf, and unrolled it would triple the kernel's code.
+__device__ __forceinline__ void finish_tail(State& s, const uint8_t* q, uint32_t rem, uint32_t total) {
+    const uint32_t* q32 = reinterpret_cast<const uint32_t*>(q);
+    const uint32_t nblk = (rem + 9 + 63) >> 6;
+#pragma nounroll
+    for (uint32_t b = 0; b < nblk; ++b) {
+        uint32_t w[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const uint32_t off = 64u * b + 4u * k;
+            uint32_t v = 0;
+            if (off + 4 <= rem) {
+                v = q32[off >> 2];
+            } else if (off < rem) {
+                for (uint32_t j = 0; off + j < rem; ++j) v |= (uint32_t)q[off + j] << (8 * j);
+            }
+            if (rem >= off && rem < off + 4) v |= 0x80u << (8 * (rem - off));
+            w[k] = sha256::bswap(v);
+        }
+        if (b + 1 == nblk) w[15] = total * 8u;  // a leaf is at most 16 KiB: the high word stays 0
+        sha256::compress(s, w);
+    }
+}
+
+__device__ __forceinline__ void store_row(uint8_t* rows, uint32_t row, const State& s) {
+    uint4* o = reinterpret_cast<uint4*>(rows + (size_t)row * 32);
+    o[0] = make_uint4(sha256::bswap(s.h[0]), sha256::bswap(s.h[1]), sha256::bswap(s.h[2]), sha256::bswap(s.h[3]));
+    o[1] = make_uint4(sha256::bswap(s.h[4]), sha256::bswap(s.h[5]), sha256::bswap(s.h[6]), sha256::bswap(s.h[7]));
+}
+
+// Lane g: leaf slot g & (width-1) of piece g >> log2_width.  kRagged: piece i
+// at base + offsets[i], lens[i] bytes; else at base + i*stride, len bytes, the
+// last piece last_len.
+template <bool kRagged>
+__global__ __launch_bounds__(kBlock) void merkle_leaf_kernel(const uint8_t* __restrict__ base, uint64_t stride,
+                                                             uint32_t len, uint32_t last_len,
+                                                             const uint64_t* __restrict__ offsets,
+                                                             const uint32_t* __restrict__ lens, uint32_t n,
+                                                             uint32_t log2_width, uint8_t* __restrict__ leaves) {
+    const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t rows = n << log2_width;
+    // Lanes past the last row redo row rows-1 (in bounds, the wave stays
+    // convergent) and store nothing.
+    const uint32_t gg = g < rows ? g : rows - 1;
+    const uint32_t piece = gg >> log2_width;
+    const uint32_t slot = gg & ((1u << log2_width) - 1);
+    const uint32_t plen = kRagged ? lens[piece] : (piece == n - 1 ? last_len : len);
+    const uint8_t* p = base + (kRagged ? offsets[piece] : (uint64_t)piece * stride);
+    const uint64_t start = (uint64_t)slot * kLeaf;
+    const uint32_t leaf_len = start < plen ? (plen - start < kLeaf ? (uint32_t)(plen - start) : kLeaf) : 0;
+    const uint32_t ng = leaf_len >> 7;
+    const uint32_t ng_wave = __builtin_amdgcn_readfirstlane(wave_max(ng));
+    p += start < plen ? start : 0;
+    State s = sha256::iv();
+    stream_groups(s, reinterpret_cast<const uint4*>(p), ng, ng_wave);
+    if (leaf_len == kLeaf) {
+        sha256::compress_const(s, kPadLeaf);
+    } else if (leaf_len) {
+        finish_tail(s, p + (size_t)ng * 128, leaf_len & 127u, leaf_len);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s.h[k] = 0;  // beyond the piece: the zero hash, not a hash of anything
+    }
+    if (g < rows) store_row(leaves, g, s);
+}
+
+// ---------------------------------------------------------------------------
+// Node reduction.
+
+// node = SHA-256(left || right); rows are big-endian bytes.
+__device__ __forceinline__ void node_hash(uint4& o0, uint4& o1, const uint4& l0, const uint4& l1, const uint4& r0,
+                                          const uint4& r1) {
+    State s = sha256::iv();
+    sha256::compress_le(s, l0, l1, r0, r1);
+    sha256::compress_const(s, kPadNode);
+    o0 = make_uint4(sha256::bswap(s.h[0]), sha256::bswap(s.h[1]), sha256::bswap(s.h[2]), sha256::bswap(s.h[3]));
+    o1 = make_uint4(sha256::bswap(s.h[4]), sha256::bswap(s.h[5]), sha256::bswap(s.h[6]), sha256::bswap(s.h[7]));
+}
+
+// Rows in LDS as two planes of uint4 (row r = lo[r] | hi[r]): a 16-byte
+// stride per lane, conflict-free ds_read_b128 / ds_write_b128.
+struct Rows {
+    uint4 lo[kTile];
+    uint4 hi[kTile];
+};
+
+// One level in place: the first 2*count rows become count rows.  Every thread
+// of the workgroup calls this (barriers inside).
+__device__ __forceinline__ void reduce_level(Rows& t, uint32_t count) {
+    const uint32_t i = threadIdx.x;
+    uint4 o0, o1;
+    if (i < count) node_hash(o0, o1, t.lo[2 * i], t.hi[2 * i], t.lo[2 * i + 1], t.hi[2 * i + 1]);
+    __syncthreads();
+    if (i < count) {
+        t.lo[i] = o0;
+        t.hi[i] = o1;
+    }
+    __syncthreads();
+}
+
+struct Row {
+    uint4 lo, hi;
+};
+
+__device__ __forceinline__ void emit_root(const Row& r, uint32_t piece, uint8_t* __restrict__ roots,
+                                          const uint8_t* __restrict__ expected, uint8_t* __restrict__ matched) {
+    if (roots) {
+        uint4* o = reinterpret_cast<uint4*>(roots + (size_t)piece * 32);
+        o[0] = r.lo;
+        o[1] = r.hi;
+    }
+    if (expected && matched) {
+        const uint32_t* x = reinterpret_cast<const uint32_t*>(expected + (size_t)piece * 32);  // 4-byte aligned
+        const bool ok = (x[0] == r.lo.x) & (x[1] == r.lo.y) & (x[2] == r.lo.z) & (x[3] == r.lo.w) &
+                        (x[4] == r.hi.x) & (x[5] == r.hi.y) & (x[6] == r.hi.z) & (x[7] == r.hi.w);
+        matched[piece] = ok ? 1 : 0;
+    }
+}
+
+// Trees of at most kTile leaves: workgroup b reduces rows [b*kTile, +kTile) =
+// pieces [b*P, +P), P = kTile >> log2_width.  After level L the root of a
+// piece with log2w == L is row (piece's first row) >> L.
+__global__ __launch_bounds__(kNodeBlock) void merkle_node_kernel(const uint8_t* __restrict__ leaves, uint32_t n,
+                                                                 uint32_t log2_width,
+                                                                 const uint8_t* __restrict__ log2w,
+                                                                 uint8_t* __restrict__ roots,
+                                                                 const uint8_t* __restrict__ expected,
+                                                                 uint8_t* __restrict__ matched) {
+    __shared__ Rows t;
+    const uint32_t i = threadIdx.x;
+    const uint32_t rows = n << log2_width;
+    const uint32_t row0 = blockIdx.x * kTile;
+    const uint4* src = reinterpret_cast<const uint4*>(leaves);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const uint32_t r = i + k * kNodeBlock;
+        const bool in = row0 + r < rows;  // (row0 + r < 2^32: rows fits 32 bits and kTile divides the grid's span)
+        t.lo[r] = in ? src[(size_t)(row0 + r) * 2] : make_uint4(0, 0, 0, 0);
+        t.hi[r] = in ? src[(size_t)(row0 + r) * 2 + 1] : make_uint4(0, 0, 0, 0);
+    }
+    __syncthreads();
+    // pieces of this tile: up to kTile of them (log2_width 0), so a thread may own two
+    const uint32_t per = kTile >> log2_width;
+    for (uint32_t L = 0;; ++L) {
+        for (uint32_t q = i; q < per; q += kNodeBlock) {
+            const uint32_t piece = blockIdx.x * per + q;
+            if (piece < n && (log2w ? log2w[piece] : log2_width) == L)
+                emit_root(Row{t.lo[(q << log2_width) >> L], t.hi[(q << log2_width) >> L]}, piece, roots, expected,
+                          matched);
+        }
+        if (L == log2_width) break;
+        reduce_level(t, kTile >> (L + 1));
+    }
+}
+
+// Trees wider than a tile: one workgroup per piece.  Each tile of kTile leaves
+// is reduced to its top, the tops (at most kMaxTops) are reduced in turn.  A
+// piece's own log2w picks its root from the first tile (log2w <= kTileLog2) or
+// from the tops.
+__global__ __launch_bounds__(kNodeBlock) void merkle_wide_node_kernel(const uint8_t* __restrict__ leaves,
+                                                                      uint32_t log2_width,
+                                                                      const uint8_t* __restrict__ log2w,
+                                                                      uint8_t* __restrict__ roots,
+                                                                      const uint8_t* __restrict__ expected,
+                                                                      uint8_t* __restrict__ matched) {
+    __shared__ Rows t;
+    __shared__ uint4 top_lo[kMaxTops], top_hi[kMaxTops];
+    const uint32_t i = threadIdx.x;
+    const uint32_t piece = blockIdx.x;
+    const uint32_t want = log2w ? log2w[piece] : log2_width;
+    // the tiles under the piece's own root (workgroup-uniform)
+    const uint32_t ntiles = want <= (uint32_t)kTileLog2 ? 1u : 1u << (want - kTileLog2);
+    if (want > log2_width) return;  // not a level of this tree: nothing to emit
+    const uint4* src = reinterpret_cast<const uint4*>(leaves) + ((size_t)piece << log2_width) * 2;
+    for (uint32_t tile = 0; tile < ntiles; ++tile) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const uint32_t r = i + k * kNodeBlock;
+            t.lo[r] = src[((size_t)tile * kTile + r) * 2];
+            t.hi[r] = src[((size_t)tile * kTile + r) * 2 + 1];
+        }
+        __syncthreads();
+        for (uint32_t L = 0;; ++L) {
+            if (tile == 0 && want == L && i == 0) emit_root(Row{t.lo[0], t.hi[0]}, piece, roots, expected, matched);
+            if (L == kTileLog2) break;
+            reduce_level(t, kTile >> (L + 1));
+        }
+        if (i == 0) {
+            top_lo[tile] = t.lo[0];
+            top_hi[tile] = t.hi[0];
+        }
+        __syncthreads();
+    }
+    if (want <= kTileLog2) return;  // (workgroup-uniform)
+    for (uint32_t k = i; k < ntiles; k += kNodeBlock) {
+        t.lo[k] = top_lo[k];
+        t.hi[k] = top_hi[k];
+    }
+    __syncthreads();
+    for (uint32_t L = kTileLog2 + 1; L <= want; ++L) reduce_level(t, (1u << want) >> L);
+    if (i == 0) emit_root(Row{t.lo[0], t.hi[0]}, piece, roots, expected, matched);
+}
+
+// One pass of a layer reduction: workgroup b reduces rows [b << levels,
+// +(1 << levels)) of the m-row input to output row b; rows at or past m are
+// the pad hash of the input's height.  levels <= kTileLog2.
+__global__ __launch_bounds__(kNodeBlock) void merkle_layer_kernel(const uint8_t* __restrict__ in, uint32_t m,
+                                                                  uint32_t levels, uint4 pad_lo, uint4 pad_hi,
+                                                                  uint8_t* __restrict__ out) {
+    __shared__ Rows t;
+    const uint32_t i = threadIdx.x;
+    const uint64_t row0 = (uint64_t)blockIdx.x << levels;
+    const uint4* src = reinterpret_cast<const uint4*>(in);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const uint32_t r = i + k * kNodeBlock;
+        const bool in_layer = row0 + r < m;
+        t.lo[r] = in_layer ? src[(row0 + r) * 2] : pad_lo;
+        t.hi[r] = in_layer ? src[(row0 + r) * 2 + 1] : pad_hi;
+    }
+    __syncthreads();
+    for (uint32_t L = 0; L < levels; ++L) reduce_level(t, (1u << levels) >> (L + 1));
+    if (i == 0) {
+        uint4* o = reinterpret_cast<uint4*>(out + (size_t)blockIdx.x * 32);
+        o[0] = t.lo[0];
+        o[1] = t.hi[0];
+    }
+}
+
+hipError_t launch_nodes(uint32_t n, uint32_t log2_width, const uint8_t* leaves, const uint8_t* log2w, uint8_t* roots,
+                        const uint8_t* expected, uint8_t* matched, hipStream_t stream) {
+    if (!roots && !(expected && matched)) return hipSuccess;
+    if (log2_width <= (uint32_t)kTileLog2) {
+        const uint64_t rows = (uint64_t)n << log2_width;
+        const uint32_t grid = (uint32_t)((rows + kTile - 1) / kTile);
+        hipLaunchKernelGGL(merkle_node_kernel, dim3(grid), dim3(kNodeBlock), 0, stream, leaves, n, log2_width, log2w,
+                           roots, expected, matched);
+    } else {
+        hipLaunchKernelGGL(merkle_wide_node_kernel, dim3(n), dim3(kNodeBlock), 0, stream, leaves, log2_width, log2w,
+                           roots, expected, matched);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_merkle_uniform(const uint8_t* base, uint64_t stride, uint32_t len, uint32_t last_len, uint32_t n,
+                                 uint32_t log2_width, uint8_t* leaves, uint8_t* roots, const uint8_t* expected,
+                                 uint8_t* matched, hipStream_t stream) {
+    const uint64_t rows = (uint64_t)n << log2_width;
+    const uint32_t grid = (uint32_t)((rows + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(merkle_leaf_kernel<false>, dim3(grid), dim3(kBlock), 0, stream, base, stride, len, last_len,
+                       (const uint64_t*)nullptr, (const uint32_t*)nullptr, n, log2_width, leaves);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_nodes(n, log2_width, leaves, nullptr, roots, expected, matched, stream);
+}
+
+hipError_t launch_merkle_ragged(const uint8_t* base, const uint64_t* offsets, const uint32_t* lens,
+                                const uint8_t* log2w, uint32_t n, uint32_t log2_width, uint8_t* leaves,
+                                uint8_t* roots, const uint8_t* expected, uint8_t* matched, hipStream_t stream) {
+    const uint64_t rows = (uint64_t)n << log2_width;
+    const uint32_t grid = (uint32_t)((rows + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(merkle_leaf_kernel<true>, dim3(grid), dim3(kBlock), 0, stream, base, (uint64_t)0, 0u, 0u,
+                       offsets, lens, n, log2_width, leaves);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_nodes(n, log2_width, leaves, log2w, roots, expected, matched, stream);
+}
+
+hipError_t launch_merkle_root(const uint8_t* layer, uint32_t n, uint8_t* work, uint8_t* root,
+                              const uint8_t (*pads)[32], hipStream_t stream) {
+    if (n == 1) return hipMemcpyAsync(root, layer, 32, hipMemcpyDeviceToDevice, stream);
+    uint32_t total = 0;  // levels to the root: log2 of n rounded up to a power of two
+    while ((1ull << total) < n) ++total;
+    const uint8_t* in = layer;
+    uint8_t* next = work;
+    uint32_t m = n, done = 0;
+    while (done < total) {
+        const uint32_t levels = total - done < (uint32_t)kTileLog2 ? total - done : (uint32_t)kTileLog2;
+        const uint32_t outs = (uint32_t)(((uint64_t)m + (1u << levels) - 1) >> levels);
+        uint8_t* out = done + levels == total ? root : next;
+        uint4 pad[2];  // rows are bytes: the words as the device loads them
+        memcpy(pad, pads[done], 32);
+        hipLaunchKernelGGL(merkle_layer_kernel, dim3(outs), dim3(kNodeBlock), 0, stream, in, m, levels, pad[0],
+                           pad[1], out);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        in = out;
+        next = out + (size_t)outs * 32;
+        m = outs;
+        done += levels;
+    }
+    return hipSuccess;
+}
+
+}  // namespace vx

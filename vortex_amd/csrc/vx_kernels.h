@@ -82,6 +82,22 @@ hipError_t launch_zero_copy(const uint64_t* srcs, const uint32_t* lens, uint32_t
                             const uint8_t* expected, uint8_t* matched, bool loader, hipStream_t stream,
                             const uint32_t* exp_index = nullptr);
 
+// BitTorrent v2 merkle kernels (sha256_kernels.hip): the leaf
+// kernel writes all n << log2_width leaf rows, the node kernel reduces each
+// piece's rows to its root (level log2w[i] when given) into roots and / or a
+// verdict against expected.
+constexpr int kMerkleMaxLog2Width = 17;
+hipError_t launch_merkle_uniform(const uint8_t* base, uint64_t stride, uint32_t len, uint32_t last_len, uint32_t n,
+                                 uint32_t log2_width, uint8_t* leaves, uint8_t* roots, const uint8_t* expected,
+                                 uint8_t* matched, hipStream_t stream);
+hipError_t launch_merkle_ragged(const uint8_t* base, const uint64_t* offsets, const uint32_t* lens,
+                                const uint8_t* log2w, uint32_t n, uint32_t log2_width, uint8_t* leaves,
+                                uint8_t* roots, const uint8_t* expected, uint8_t* matched, hipStream_t stream);
+// Root of a layer of n >= 1 hashes; pads[k] = the pad hash of the layer's
+// height + k (one per level to the root); work: 32*n bytes.
+hipError_t launch_merkle_root(const uint8_t* layer, uint32_t n, uint8_t* work, uint8_t* root,
+                              const uint8_t (*pads)[32], hipStream_t stream);
+
 hipError_t launch_synth_fill(uint8_t* base, uint64_t stride, uint32_t len, uint32_t n, uint64_t first,
                              uint64_t seed, uint32_t corrupt_every, hipStream_t stream);
 

@@ -169,6 +169,154 @@ def sha1_ragged(data: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor,
     return digests, matched
 
 
+def _merkle_outputs(n: int, log2_width: int, dev, expected, leaves, roots, matched):
+    """Allocate / check the output tensors of a merkle call."""
+    if not 0 <= log2_width <= 17:
+        raise ValueError("log2_width must be 0..17")
+    rows = n << log2_width
+    if rows >> 32:
+        raise ValueError("n << log2_width must fit 32 bits")
+    if leaves is None:
+        leaves = torch.empty((rows, 32), dtype=torch.uint8, device=dev)
+    else:
+        _req(leaves, "leaves")
+        if leaves.numel() < 32 * rows or leaves.device != dev:
+            raise ValueError("leaves must hold (n << log2_width)*32 bytes on the data's device")
+    if roots is None:
+        roots = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    else:
+        _req(roots, "roots")
+        if roots.numel() < 32 * n or roots.device != dev:
+            raise ValueError("roots must hold n*32 bytes on the data's device")
+    if expected is not None:
+        _req(expected, "expected")
+        if expected.numel() < 32 * n or expected.device != dev:
+            raise ValueError("expected must hold n*32 bytes on the data's device")
+        if matched is None:
+            matched = torch.empty((n,), dtype=torch.uint8, device=dev)
+        else:
+            _req(matched, "matched")
+            if matched.numel() < n or matched.device != dev:
+                raise ValueError("matched must hold n bytes on the data's device")
+    else:
+        matched = None
+    return leaves, roots, matched
+
+
+def merkle_uniform(data: torch.Tensor, n: int, piece_len: int, log2_width: int, stride: Optional[int] = None,
+                   last_len: Optional[int] = None, expected: Optional[torch.Tensor] = None,
+                   leaves: Optional[torch.Tensor] = None, roots: Optional[torch.Tensor] = None,
+                   matched: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None):
+    """BitTorrent v2 roots of n pieces at data[i*stride : i*stride+piece_len]
+    (the last one last_len bytes), each a SHA-256 merkle tree of
+    2^log2_width 16 KiB leaf slots (vx_merkle_device_uniform).
+
+    Returns (roots [n,32], leaves [n << log2_width, 32], matched [n] or None).
+    Every leaf row is written, zero rows included.  Enqueue-only."""
+    _req(data, "data")
+    stride = piece_len if stride is None else stride
+    last_len = piece_len if last_len is None else last_len
+    if n and (n - 1) * stride + last_len > data.numel():
+        raise ValueError("batch exceeds data tensor")
+    dev = data.device
+    leaves, roots, matched = _merkle_outputs(n, log2_width, dev, expected, leaves, roots, matched)
+    rc = lib().vx_merkle_device_uniform(data.data_ptr(), stride, piece_len, last_len, n, log2_width,
+                                        leaves.data_ptr(), roots.data_ptr(),
+                                        expected.data_ptr() if expected is not None else None,
+                                        matched.data_ptr() if matched is not None else None,
+                                        _stream_ptr(stream, dev))
+    check(rc, "vx_merkle_device_uniform")
+    return roots, leaves, matched
+
+
+def _check_merkle_layout(data: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor,
+                         log2w: Optional[torch.Tensor], log2_width: int) -> None:
+    """What :func:`_check_ragged_layout` checks for sha1_ragged, for a merkle
+    batch: offsets 16-byte aligned and >= 0, lengths >= 0, every piece inside
+    `data`, every log2w <= log2_width and every piece inside its own tree
+    (16384 << log2w bytes).  One device reduction and one copy back (a sync)."""
+    if offsets.numel() == 0:
+        return
+    ends = offsets + lens.to(torch.int64)
+    lw = log2w.to(torch.int64) if log2w is not None else torch.full_like(offsets, log2_width)
+    stats = torch.stack([
+        (offsets & 15).ne(0).any().to(torch.int64),
+        offsets.min().lt(0).to(torch.int64) + lens.min().lt(0).to(torch.int64),
+        ends.max(),
+        lw.max(),
+        (lens.to(torch.int64) > torch.bitwise_left_shift(torch.full_like(lw, 16384), lw.clamp(0, 17))).any().to(torch.int64),
+    ]).cpu().tolist()
+    if stats[0]:
+        raise ValueError("merkle_ragged: every offset must be a multiple of 16 (the kernels load 16 bytes per lane)")
+    if stats[1]:
+        raise ValueError("merkle_ragged: negative offset or length")
+    if stats[2] > data.numel():
+        raise ValueError(f"merkle_ragged: a piece ends at byte {stats[2]}, past the data tensor "
+                         f"({data.numel()} bytes)")
+    if stats[3] > log2_width:
+        raise ValueError(f"merkle_ragged: log2w {stats[3]} > log2_width {log2_width}")
+    if stats[4]:
+        raise ValueError("merkle_ragged: a piece is longer than its tree (16384 << log2w bytes)")
+
+
+def merkle_ragged(data: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor, log2_width: int,
+                  log2w: Optional[torch.Tensor] = None, expected: Optional[torch.Tensor] = None,
+                  leaves: Optional[torch.Tensor] = None, roots: Optional[torch.Tensor] = None,
+                  matched: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                  validate: bool = True):
+    """BitTorrent v2 roots of piece i = data[offsets[i] : offsets[i]+lens[i]]
+    (vx_merkle_device_ragged).  offsets: int64 device tensor (16-byte aligned
+    values); lens: int32; log2w: optional uint8, piece i's own tree width
+    (<= log2_width; merkle.file_pieces).  Piece i's leaf rows start at row
+    i << log2_width whatever its log2w.  validate: as for :func:`sha1_ragged`.
+
+    Returns (roots [n,32], leaves [n << log2_width, 32], matched [n] or None)."""
+    _req(data, "data")
+    _req(offsets, "offsets", torch.int64)
+    _req(lens, "lens", torch.int32)
+    n = offsets.numel()
+    if lens.numel() != n:
+        raise ValueError("offsets and lens differ in length")
+    if log2w is not None:
+        _req(log2w, "log2w")
+        if log2w.numel() != n:
+            raise ValueError("log2w must hold n widths")
+    dev = data.device
+    for name, t in (("offsets", offsets), ("lens", lens), ("log2w", log2w)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, data on {dev}")
+    leaves, roots, matched = _merkle_outputs(n, log2_width, dev, expected, leaves, roots, matched)
+    if validate:
+        _check_merkle_layout(data, offsets, lens, log2w, log2_width)
+    rc = lib().vx_merkle_device_ragged(data.data_ptr(), offsets.data_ptr(), lens.data_ptr(),
+                                       log2w.data_ptr() if log2w is not None else None, n, log2_width,
+                                       leaves.data_ptr(), roots.data_ptr(),
+                                       expected.data_ptr() if expected is not None else None,
+                                       matched.data_ptr() if matched is not None else None,
+                                       _stream_ptr(stream, dev))
+    check(rc, "vx_merkle_device_ragged")
+    return roots, leaves, matched
+
+
+def merkle_root(layer: torch.Tensor, height: int = 0, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """Root of a layer of hashes ([n,32] uint8) standing `height` levels above
+    the leaves, padded to a power of two with pad hashes
+    (vx_merkle_device_root).  Returns a [32] uint8 tensor.  Enqueue-only."""
+    _req(layer, "layer")
+    if layer.numel() == 0 or layer.numel() % 32:
+        raise ValueError("layer must hold n >= 1 hashes of 32 bytes")
+    n = layer.numel() // 32
+    dev = layer.device
+    work = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    root = torch.empty((32,), dtype=torch.uint8, device=dev)
+    if stream is not None:  # the scratch outlives this call on the stream that uses it
+        work.record_stream(stream)
+    rc = lib().vx_merkle_device_root(layer.data_ptr(), n, height, work.data_ptr(), root.data_ptr(),
+                                     _stream_ptr(stream, dev))
+    check(rc, "vx_merkle_device_root")
+    return root
+
+
 def ragged_plan(lens_host) -> tuple[int, int]:
     """(longest piece, total bytes) of a ragged batch: the `plan` argument of
     :func:`sha1_ragged`."""

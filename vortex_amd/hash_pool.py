@@ -329,6 +329,26 @@ class HashPool:
         raw = dig.raw
         return [bool(b) for b in matched.raw[:n]], [raw[20 * i: 20 * i + 20] for i in range(n)]
 
+    def verify_merkle(self, pieces: Sequence, expected: Sequence[bytes], piece_length: int,
+                      log2w: Optional[Sequence[int]] = None) -> tuple[list[bool], list[bytes]]:
+        """BitTorrent v2 (BEP 52) bulk verify (vx_merkle_verify_batch): piece i
+        against expected[i], the 32-byte root of its SHA-256 merkle tree over
+        16 KiB blocks (a `piece layers` entry; for a file of at most
+        piece_length bytes its `pieces root`, with log2w[i] from
+        merkle.file_pieces).  Returns (verdicts, roots)."""
+        n = len(pieces)
+        if len(expected) != n or (log2w is not None and len(log2w) != n):
+            raise ValueError("expected (and log2w) must have one entry per piece")
+        ptrs, lens, keep = _ptr_arrays(pieces)
+        exp = ctypes.create_string_buffer(b"".join(bytes(e) for e in expected), 32 * max(n, 1))
+        lw = (ctypes.c_uint8 * max(n, 1))(*log2w) if log2w is not None else None
+        matched = ctypes.create_string_buffer(max(n, 1))
+        roots = ctypes.create_string_buffer(32 * max(n, 1))
+        check(self.lib.vx_merkle_verify_batch(self._h, ptrs, lens, lw, n, piece_length, exp, matched, roots),
+              "vx_merkle_verify_batch", self.lib)
+        raw = roots.raw
+        return [bool(b) for b in matched.raw[:n]], [raw[32 * i: 32 * i + 32] for i in range(n)]
+
 
 def _verify_files(pool: "HashPool", paths: Sequence[str], file_lengths: Sequence[int], piece_length: int,
                   expected: bytes, io_threads: int = 0, first: int = 0,
