@@ -552,6 +552,48 @@ int vx_merkle_verify_batch(vx_ctx* ctx, const uint8_t* const* ptrs, const uint32
                            size_t n, uint32_t piece_length, const uint8_t* expected, uint8_t* matched_out,
                            uint8_t* roots_out);
 
+/* The two halves of the device entries on their own, for a caller that
+ * streams blocks in rounds of its own (the re-verify below does).
+ * Stage block b at d_stage + b*VX_MERKLE_BLOCK, d_lens[b] bytes; its leaf goes to row d_rows[b] of d_leaves
+ * (0xFFFFFFFF: skipped; d_lens[b] == 0: the zero hash).  d_stage 16-byte aligned.
+ * A block of length 0 or a skipped one is never read, so such entries may lie
+ * past the end of the stage.  d_lens[b] <= VX_MERKLE_BLOCK and the rows are
+ * device-resident and not checked here; vortex_amd.device.merkle_blocks
+ * checks them.  Enqueue-only; n_blocks == 0 launches nothing. */
+int vx_merkle_device_blocks(const void* d_stage, const uint32_t* d_rows, const uint32_t* d_lens,
+                            uint32_t n_blocks, void* d_leaves, void* stream);
+/* Reduce leaf rows that are already on the device: piece i's rows start at row i << log2_width, its tree has
+ * 2^d_log2w[i] slots (NULL: log2_width).  roots / expected / matched as for vx_merkle_device_ragged. */
+int vx_merkle_device_nodes(const void* d_leaves, const uint8_t* d_log2w, uint32_t n, uint32_t log2_width,
+                           void* d_roots, const void* d_expected, void* d_matched, void* stream);
+
+/* Re-verify a v2 torrent's files from disk: the v2 counterpart of
+ * vx_verify_files.  Layout (BEP 52): every file starts its own pieces and no
+ * piece spans files; pieces are numbered file by file in the order given; an
+ * empty file has none; a file longer than piece_length has
+ * ceil(len / piece_length) pieces of full width (expected rows: its `piece
+ * layers`); a file of at most piece_length bytes is one piece as wide as its
+ * block count rounded up to a power of two (expected row: its `pieces
+ * root`).  n_pieces must equal that sum.  piece_length is a power of two from
+ * VX_MERKLE_BLOCK to 2 GiB and is NOT bounded by max_piece_len or slot_bytes:
+ * the files are streamed in rounds of 16 KiB blocks, cut wherever a slot's
+ * stage is full, and only the finished 32-byte leaf rows are kept (in a device
+ * window of 512 bytes x max(blocks per round, piece_length / 16 KiB)).
+ * matched_out[i] = 1 iff every byte of piece i was read and its root equals
+ * expected[32*i..]; a missing, short or unreadable file gives 0 for exactly
+ * the pieces that lack bytes, and the return value counts those pieces (as
+ * vx_verify_files).  io_threads 0 = a default.  VX_EBUSY while async pieces
+ * are pending.  Counts into vx_get_stats and fills vx_last_verify
+ * (chunk_bytes = a round's bytes); vx_last_verify_rounds returns 0. */
+int64_t vx_merkle_verify_files(vx_ctx* ctx, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                               uint32_t piece_length, const uint8_t* expected, size_t n_pieces,
+                               uint8_t* matched_out, uint32_t io_threads);
+/* Pieces [first, first + count) only, reading only their bytes (one rank's
+ * shard); expected is the whole table, matched_out has count entries. */
+int64_t vx_merkle_verify_files_range(vx_ctx* ctx, const char* const* paths, const uint64_t* file_lengths,
+                                     size_t nfiles, uint32_t piece_length, const uint8_t* expected, size_t n_pieces,
+                                     size_t first, size_t count, uint8_t* matched_out, uint32_t io_threads);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,13 @@ One condition: on 1,024 x 4 MiB the merkle path must be at least 2x the SHA-1
 ragged rate measured beside it (a piece is 256 independent lanes instead of
 one chain); the ratio is recorded and the tool exits 1 below it.
 
+--blocks-leg K: on 65,536 x 256 KiB the block-stream kernel and the node entry
+(merkle_blocks + merkle_nodes, the re-verify's kernels) run over the same
+buffer beside merkle_uniform, K timed runs of each, alternating; both are
+recorded with the spread between merkle_uniform's own runs.
+
   python tools/merkle_bench.py --out profiles/merkle/device.json [--isa sha256_kernels.s]
+  python tools/merkle_bench.py --shapes 0 --blocks-leg 3 --out profiles/merkle/blocks.json
 """
 from __future__ import annotations
 
@@ -121,6 +127,9 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--target-ms", type=float, default=400.0, help="timed window per kernel and shape")
     ap.add_argument("--shapes", default="0,1,2", help="indices into the three shapes")
+    ap.add_argument("--blocks-leg", type=int, default=0, metavar="K",
+                    help="on 65,536 x 256 KiB also run merkle_blocks + merkle_nodes beside merkle_uniform, "
+                         "K alternating timed runs of each")
     args = ap.parse_args()
 
     isa = isa_valu_per_block(args.isa) if args.isa else None
@@ -170,6 +179,40 @@ def main() -> int:
         t, clock = timed(merkle, args.warmup, steps, dev)
         shape = {"pieces": n, "piece_len": plen, "bytes": nbytes, "log2_width": log2_width,
                  "merkle": record(t, clock, nbytes, n << log2_width, BLOCK // 64, valu256, simds)}
+
+        if idx == 0 and args.blocks_leg:
+            # The block-stream kernel + the node entry over the same buffer,
+            # rows piece-major so both write the same leaves: merkle_uniform
+            # (unchanged code) and the pair alternate, --blocks-leg times each;
+            # the spread between merkle_uniform's own runs is the margin.
+            nb = n << log2_width
+            b_rows = torch.arange(nb, dtype=torch.int32, device=dev)
+            b_lens = torch.full((nb,), BLOCK, dtype=torch.int32, device=dev)
+            b_leaves = torch.full((nb, 32), 0xFF, dtype=torch.uint8, device=dev)
+            b_roots = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+            vdev.merkle_blocks(data, b_rows, b_lens, b_leaves)  # validates the tables once
+
+            def blocks():
+                vdev.merkle_blocks(data, b_rows, b_lens, b_leaves, validate=False)
+                vdev.merkle_nodes(b_leaves, n, log2_width, roots=b_roots)
+
+            blocks()
+            torch.cuda.synchronize(dev)
+            if not (torch.equal(b_leaves, leaves) and torch.equal(b_roots, roots)):
+                raise SystemExit(f"{n} x {plen}: blocks + nodes differ from merkle_uniform")
+            runs = {"merkle_uniform": [], "blocks_nodes": []}
+            for _ in range(args.blocks_leg):
+                for name, fn in (("merkle_uniform", merkle), ("blocks_nodes", blocks)):
+                    t, clock = timed(fn, args.warmup, steps, dev)
+                    runs[name].append(record(t, clock, nbytes, nb, BLOCK // 64, valu256, simds))
+            rates = {k: [r["GiB_per_s"] for r in v] for k, v in runs.items()}
+            shape["blocks_leg"] = {
+                "runs": runs, "GiB_per_s": rates,
+                "merkle_uniform_spread": round(max(rates["merkle_uniform"]) - min(rates["merkle_uniform"]), 1),
+                "blocks_minus_uniform_median": round(
+                    sorted(rates["blocks_nodes"])[len(rates["blocks_nodes"]) // 2] -
+                    sorted(rates["merkle_uniform"])[len(rates["merkle_uniform"]) // 2], 1)}
+            del b_rows, b_lens, b_leaves, b_roots
 
         if sha1_kind:
             digests = torch.empty((n, 20), dtype=torch.uint8, device=dev)

@@ -52,6 +52,7 @@ EXPORTS = (
     "vx_verify_files_split_multi",
     "vx_merkle_device_uniform", "vx_merkle_device_ragged", "vx_merkle_device_root", "vx_merkle_pad_hash",
     "vx_merkle_verify_batch",
+    "vx_merkle_device_blocks", "vx_merkle_device_nodes", "vx_merkle_verify_files", "vx_merkle_verify_files_range",
 )
 # ... plus include/vx_tuning.h and include/vx_synth.h: libvortex_amd_tuning.so only.
 TUNING_EXPORTS = (
@@ -193,6 +194,11 @@ def _declare(L: ctypes.CDLL, tuning: bool = False) -> None:
         "vx_merkle_device_root": ([vp, c.c_uint32, c.c_uint32, vp, vp, vp], c.c_int),
         "vx_merkle_pad_hash": ([c.c_uint32, vp], c.c_int),
         "vx_merkle_verify_batch": ([vp, vp, vp, vp, c.c_size_t, c.c_uint32, vp, vp, vp], c.c_int),
+        "vx_merkle_device_blocks": ([vp, vp, vp, c.c_uint32, vp, vp], c.c_int),
+        "vx_merkle_device_nodes": ([vp, vp, c.c_uint32, c.c_uint32, vp, vp, vp, vp], c.c_int),
+        "vx_merkle_verify_files": ([vp, vp, vp, c.c_size_t, c.c_uint32, vp, c.c_size_t, vp, c.c_uint32], c.c_int64),
+        "vx_merkle_verify_files_range": ([vp, vp, vp, c.c_size_t, c.c_uint32, vp, c.c_size_t, c.c_size_t,
+                                          c.c_size_t, vp, c.c_uint32], c.c_int64),
     }
     if tuning:
         sig.update({

@@ -154,6 +154,43 @@ __global__ __launch_bounds__(kBlock) void merkle_leaf_kernel(const uint8_t* __re
     if (g < rows) store_row(leaves, g, s);
 }
 
+// Block stream (the re-verify from disk): lane b hashes stage
+// block b, lens[b] bytes at stage + b*16 KiB, into leaf row rows[b].  A launch
+// is tied to no piece and no width: the host cuts a round wherever its stage
+// is full and says where each block's row lies.  lens[b] == 0 is an absent
+// slot (the zero hash; its stage bytes are never read, it need not have any);
+// rows[b] == kSkipRow is a hole in the stage and stores nothing.  The streaming
+// is the leaf kernel's: two-group ring, wave-uniform bound, clamped loads, so
+// a wave of full blocks runs the ring and the constant padding block only and
+// a wave of tails skips the ring.
+constexpr uint32_t kSkipRow = 0xFFFFFFFFu;
+
+__global__ __launch_bounds__(kBlock) void merkle_block_kernel(const uint8_t* __restrict__ stage,
+                                                              const uint32_t* __restrict__ rows,
+                                                              const uint32_t* __restrict__ lens, uint32_t n_blocks,
+                                                              uint8_t* __restrict__ leaves) {
+    const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
+    // Lanes past the last block redo it (in bounds, the wave stays convergent)
+    // and store nothing.
+    const uint32_t b = g < n_blocks ? g : n_blocks - 1;
+    const uint32_t row = rows[b];
+    const uint32_t leaf_len = row == kSkipRow ? 0 : lens[b];
+    const uint8_t* p = stage + (size_t)b * kLeaf;
+    const uint32_t ng = leaf_len >> 7;
+    const uint32_t ng_wave = __builtin_amdgcn_readfirstlane(wave_max(ng));
+    State s = sha256::iv();
+    stream_groups(s, reinterpret_cast<const uint4*>(p), ng, ng_wave);
+    if (leaf_len == kLeaf) {
+        sha256::compress_const(s, kPadLeaf);
+    } else if (leaf_len) {
+        finish_tail(s, p + (size_t)ng * 128, leaf_len & 127u, leaf_len);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s.h[k] = 0;  // an absent slot: the zero hash, not a hash of anything
+    }
+    if (g < n_blocks && row != kSkipRow) store_row(leaves, row, s);
+}
+
 // ---------------------------------------------------------------------------
 // Node reduction.
 
@@ -355,6 +392,18 @@ hipError_t launch_merkle_ragged(const uint8_t* base, const uint64_t* offsets, co
                        offsets, lens, n, log2_width, leaves);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    return launch_nodes(n, log2_width, leaves, log2w, roots, expected, matched, stream);
+}
+
+hipError_t launch_merkle_blocks(const uint8_t* stage, const uint32_t* rows, const uint32_t* lens, uint32_t n_blocks,
+                                uint8_t* leaves, hipStream_t stream) {
+    const uint32_t grid = (uint32_t)(((uint64_t)n_blocks + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(merkle_block_kernel, dim3(grid), dim3(kBlock), 0, stream, stage, rows, lens, n_blocks, leaves);
+    return hipGetLastError();
+}
+
+hipError_t launch_merkle_nodes(const uint8_t* leaves, const uint8_t* log2w, uint32_t n, uint32_t log2_width,
+                               uint8_t* roots, const uint8_t* expected, uint8_t* matched, hipStream_t stream) {
     return launch_nodes(n, log2_width, leaves, log2w, roots, expected, matched, stream);
 }
 

@@ -46,6 +46,7 @@
 #include "vx_files.hpp"
 #include "vx_hash.h"
 #include "vx_kernels.h"
+#include "vx_merkle_rounds.hpp"
 #include "vx_synth.h"
 #include "vx_tuning.h"
 
@@ -292,7 +293,21 @@ struct vx_ctx {
     };
     std::vector<MerkleBufs> merkle;
     uint32_t merkle_rows = 0;
-    uint64_t verify_t0_ns = 0;                 // the running re-verify call's start (steady clock)
+    // vx_merkle_verify_files: the leaf-row window, per slot the pinned and
+    // device rows | lens tables of a round, the per-call device rows
+    // (expected | verdict | log2w per piece) and the event that orders one
+    // round's kernels after the last round's; all kept across calls and grown
+    // on demand.
+    struct MerkleFiles {
+        uint8_t* d_window = nullptr;
+        uint64_t window_rows = 0;
+        std::vector<uint32_t*> h_tab, d_tab;
+        uint64_t tab_entries = 0;
+        uint8_t* d_call = nullptr;
+        uint64_t call_cap = 0;
+        hipEvent_t chain = nullptr;
+    } mfiles;
+    uint64_t verify_t0_ns = 0;                // the running re-verify call's start (steady clock)
 };
 
 namespace {
@@ -369,6 +384,20 @@ void free_stage(Slot& s) {
     }
     s.h_stage = nullptr;
     s.stage_map = 0;
+}
+
+// The buffers of vx_merkle_verify_files (not its event).
+void free_merkle_files(vx_ctx* c) {
+    vx_ctx::MerkleFiles& m = c->mfiles;
+    if (m.d_window) (void)hipFree(m.d_window);
+    if (m.d_call) (void)hipFree(m.d_call);
+    for (uint32_t* p : m.h_tab)
+        if (p) (void)hipHostFree(p);
+    for (uint32_t* p : m.d_tab)
+        if (p) (void)hipFree(p);
+    hipEvent_t chain = m.chain;
+    m = vx_ctx::MerkleFiles{};
+    m.chain = chain;
 }
 
 int free_slot_mem(Slot& s) {
@@ -991,6 +1020,8 @@ int vx_destroy(vx_ctx* c) {
         if (m.d) (void)hipFree(m.d);
         if (m.h) (void)hipHostFree(m.h);
     }
+    free_merkle_files(c);
+    if (c->mfiles.chain) (void)hipEventDestroy(c->mfiles.chain);
     if (c->chunk_prev) (void)hipEventDestroy(c->chunk_prev);
     for (hipEvent_t e : c->copy_ev)
         if (e) (void)hipEventDestroy(e);
@@ -3305,6 +3336,280 @@ int vx_merkle_verify_batch(vx_ctx* c, const uint8_t* const* ptrs, const uint32_t
     c->stats.bytes_completed += n_bytes;
     c->stats.batches += n_rounds;
     return 0;
+}
+
+int vx_merkle_device_blocks(const void* d_stage, const uint32_t* d_rows, const uint32_t* d_lens, uint32_t n_blocks,
+                            void* d_leaves, void* stream) {
+    if (n_blocks == 0) return 0;
+    if (!d_stage || !d_rows || !d_lens || !d_leaves) return fail(VX_EINVAL, "vx_merkle_device_blocks: NULL argument");
+    if ((reinterpret_cast<uintptr_t>(d_stage) | reinterpret_cast<uintptr_t>(d_leaves)) & 15)
+        return fail(VX_EINVAL, "vx_merkle_device_blocks: d_stage and d_leaves must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_rows) | reinterpret_cast<uintptr_t>(d_lens)) & 3)
+        return fail(VX_EINVAL, "vx_merkle_device_blocks: d_rows and d_lens must be 4-byte aligned");
+    hipError_t e = vx::launch_merkle_blocks(static_cast<const uint8_t*>(d_stage), d_rows, d_lens, n_blocks,
+                                            static_cast<uint8_t*>(d_leaves), static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "merkle block kernel launch");
+    return 0;
+}
+
+int vx_merkle_device_nodes(const void* d_leaves, const uint8_t* d_log2w, uint32_t n, uint32_t log2_width,
+                           void* d_roots, const void* d_expected, void* d_matched, void* stream) {
+    if (n == 0) return 0;
+    int rc = merkle_args("vx_merkle_device_nodes", d_leaves, d_leaves, n, log2_width);
+    if (rc) return rc;
+    if ((reinterpret_cast<uintptr_t>(d_roots) & 15) || (reinterpret_cast<uintptr_t>(d_expected) & 3))
+        return fail(VX_EINVAL, "vx_merkle_device_nodes: d_roots must be 16-byte and d_expected 4-byte aligned");
+    const bool verdict = d_expected && d_matched;
+    hipError_t e = vx::launch_merkle_nodes(static_cast<const uint8_t*>(d_leaves), d_log2w, n, log2_width,
+                                           static_cast<uint8_t*>(d_roots),
+                                           verdict ? static_cast<const uint8_t*>(d_expected) : nullptr,
+                                           verdict ? static_cast<uint8_t*>(d_matched) : nullptr,
+                                           static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "merkle node kernel launch");
+    return 0;
+}
+
+// ---- vx_merkle_verify_files: the v2 re-verify from disk ----
+// Rounds of 16 KiB blocks packed by vx_merkle::Rounds, one slot's pinned stage
+// each.  Per round, on the slot's stream: the data H2D, the rows | lens table
+// in one H2D, the block kernel, and the node kernels of the groups of pieces
+// the round finished, with verdicts into the call's device rows; the kernels
+// wait for the previous round's (one event), the copies do not.  Reads run up
+// to kReadahead rounds ahead of the round being enqueued.
+
+constexpr uint64_t kMerkleRoundCap = 64ull << 20;  // a round's stage bytes at most
+constexpr uint32_t kMerkleRunBlocks = 128;         // one pread: 2 MiB at most (32 reads for 16 readers per full round)
+
+static int ensure_merkle_files(vx_ctx* c, uint64_t window_rows, uint64_t entries, uint64_t count) {
+    vx_ctx::MerkleFiles& m = c->mfiles;
+    const char* oom = "vx_merkle_verify_files: buffer allocation failed";
+    if (!m.chain && hipEventCreateWithFlags(&m.chain, hipEventDisableTiming) != hipSuccess)
+        return fail(VX_EDEVICE, "vx_merkle_verify_files: event creation failed");
+    if (m.window_rows < window_rows) {
+        if (m.d_window) (void)hipFree(m.d_window);
+        m.d_window = nullptr;
+        m.window_rows = 0;
+        if (hipMalloc(&m.d_window, window_rows * 32) != hipSuccess) return fail(VX_ENOMEM, oom);
+        m.window_rows = window_rows;
+    }
+    if (m.tab_entries < entries || m.h_tab.size() != c->slots.size()) {
+        for (uint32_t* p : m.h_tab)
+            if (p) (void)hipHostFree(p);
+        for (uint32_t* p : m.d_tab)
+            if (p) (void)hipFree(p);
+        m.h_tab.assign(c->slots.size(), nullptr);
+        m.d_tab.assign(c->slots.size(), nullptr);
+        m.tab_entries = 0;
+        for (size_t k = 0; k < c->slots.size(); ++k)
+            if (hipHostMalloc(&m.h_tab[k], entries * 8, hipHostMallocDefault) != hipSuccess ||
+                hipMalloc(&m.d_tab[k], entries * 8) != hipSuccess)
+                return fail(VX_ENOMEM, oom);
+        m.tab_entries = entries;
+    }
+    if (m.call_cap < count) {
+        if (m.d_call) (void)hipFree(m.d_call);
+        m.d_call = nullptr;
+        m.call_cap = 0;
+        const uint64_t cap = std::max<uint64_t>(count, 4096);
+        if (hipMalloc(&m.d_call, cap * 34) != hipSuccess) return fail(VX_ENOMEM, oom);
+        m.call_cap = cap;
+    }
+    return 0;
+}
+
+static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                                 uint32_t piece_length, const uint8_t* expected, size_t n_pieces, size_t first,
+                                 size_t count, uint8_t* matched_out, uint32_t io_threads) {
+    const char* who = "vx_merkle_verify_files";
+    if (!c) return fail(VX_EINVAL, std::string(who) + ": NULL context");
+    if ((nfiles && (!paths || !file_lengths)) || (n_pieces && !expected) || (count && !matched_out))
+        return fail(VX_EINVAL, std::string(who) + ": NULL paths/file_lengths/expected/matched_out");
+    if (piece_length < VX_MERKLE_BLOCK || (piece_length & (piece_length - 1)))
+        return fail(VX_EINVAL, std::string(who) + ": piece_length must be a power of two >= 16384");
+    if (n_pieces != vx_merkle::torrent_pieces(file_lengths, nfiles, piece_length))
+        return fail(VX_EINVAL, std::string(who) + ": n_pieces does not match the files");
+    if (first > n_pieces || count > n_pieces - first)
+        return fail(VX_EINVAL, std::string(who) + ": piece range outside the torrent");
+    if (c->pending) return fail(VX_EBUSY, std::string(who) + ": async pieces pending; drain and poll first");
+    if (c->sticky) return c->sticky;
+    if (c->filling >= 0) {  // an empty filling slot (pending == 0): hand it back
+        c->slots[c->filling].state = Slot::FREE;
+        c->filling = -1;
+    }
+    for (auto& s : c->slots)
+        if (s.state != Slot::FREE) return fail(VX_EBUSY, std::string(who) + ": a batch is in flight");
+    if (count == 0) return 0;
+    const uint64_t bpr64 = std::min<uint64_t>(c->slots[0].arena_cap, kMerkleRoundCap) / VX_MERKLE_BLOCK;
+    if (bpr64 == 0) return fail(VX_ERANGE, std::string(who) + ": a slot holds no 16 KiB block");
+    const uint32_t bpr = (uint32_t)bpr64;
+    int rc = set_device(c);
+    if (rc) return rc;
+    const uint32_t R = vx_merkle::Rounds::window_for(bpr, piece_length);
+    const uint32_t entries = 2 * bpr + piece_length / VX_MERKLE_BLOCK;
+    if ((rc = ensure_merkle_files(c, R, entries, count))) return rc;
+    vx_ctx::MerkleFiles& mf = c->mfiles;
+    uint8_t* d_exp = mf.d_call;
+    uint8_t* d_match = mf.d_call + mf.call_cap * 32;
+    uint8_t* d_lw = mf.d_call + mf.call_cap * 33;
+
+    const uint64_t t_call = vx_files::Readers::now_ns();
+    c->last_verify = vx_verify_trace{};
+    c->last_rounds.clear();
+    c->verify_t0_ns = t_call;
+    {
+        std::vector<uint8_t> lw(count);
+        vx_merkle::PieceCursor pc(file_lengths, nfiles, piece_length);
+        pc.seek(first);
+        for (size_t i = 0; i < count; ++i, pc.next()) lw[i] = (uint8_t)pc.log2w();
+        if (hipMemcpy(d_exp, expected + 32 * first, count * 32, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_lw, lw.data(), count, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemset(d_match, 0, count) != hipSuccess ||
+            hipStreamSynchronize(nullptr) != hipSuccess)  // (the slot streams do not wait for the null stream)
+            return fail(VX_EDEVICE, std::string(who) + ": expected-table upload failed");
+    }
+    std::vector<int> fds(nfiles, -1);
+    for (size_t f = 0; f < nfiles; ++f) fds[f] = open(paths[f], O_RDONLY | O_CLOEXEC);
+    const int nthreads = io_threads ? (int)io_threads : (int)std::max(1u, std::min(16u, usable_cpus()));
+    std::vector<uint8_t> bad(count, 0);
+    std::memset(matched_out, 0, count);
+    const size_t nslots = c->slots.size();
+    // Reads run ahead as far as the slots allow: a v2 round carries no state,
+    // so a slot is free again as soon as its own round's kernels are done, and
+    // only the round about to be enqueued ever waits for one.
+    const size_t depth = nslots - 1;
+    uint64_t n_rounds = 0, n_bytes = 0, copy_bytes = 0;
+    using clk = std::chrono::steady_clock;
+    auto t_last_enqueue = clk::now();
+    {
+        const std::vector<vx_files::FileSpan> no_spans;
+        const vx_files::DirectIo dio(fds, c->cfg.direct_io != 0);
+        vx_files::Readers rd(nthreads, no_spans, fds, piece_length, bad.data(), first, &dio, true);
+        vx_merkle::Rounds pack(file_lengths, nfiles, piece_length, first, count, bpr, R, entries, kMerkleRunBlocks);
+        std::vector<vx_merkle::Round> round(nslots);
+        std::vector<std::vector<vx_files::ReadItem>> items(nslots);
+        std::vector<uint64_t> ticket(nslots, 0);
+        std::vector<uint8_t> live(nslots, 0);  // the slot carries an enqueued round
+        bool more = true, have_prev = false;
+        size_t nr = 0;  // next round to read
+        for (size_t ne = 0; !rc; ++ne) {
+            while (more && nr <= ne + depth && !rc) {
+                const size_t si = nr % nslots;
+                Slot& s = c->slots[si];
+                if (live[si]) {  // the round this slot carried: its stage and tables are free again after it
+                    const hipError_t q = nr == ne ? hipEventSynchronize(s.done) : hipEventQuery(s.done);
+                    if (q == hipErrorNotReady) break;  // read-ahead takes only a slot that is free now
+                    if (q != hipSuccess) {
+                        rc = fail(VX_EDEVICE, std::string(who) + ": wait failed");
+                        break;
+                    }
+                    live[si] = 0;
+                }
+                if (!(more = pack.next(round[si]))) break;
+                if ((rc = ensure_stage(c, s))) break;
+                auto& it = items[si];
+                it.clear();
+                for (const vx_merkle::Read& r : round[si].reads) {
+                    vx_files::ReadItem x{s.h_stage + (uint64_t)r.stage_block * VX_MERKLE_BLOCK, r.piece, 0, r.len};
+                    x.file = (int32_t)r.file;
+                    x.file_off = (int64_t)r.file_off;
+                    it.push_back(x);
+                }
+                ticket[si] = rd.submit(it);
+                ++nr;
+            }
+            if (rc || ne == nr) break;
+            const size_t si = ne % nslots;
+            Slot& s = c->slots[si];
+            const vx_merkle::Round& r = round[si];
+            rd.wait(ticket[si]);
+            const uint32_t m = (uint32_t)r.rows.size();
+            uint32_t* h_tab = mf.h_tab[si];
+            uint32_t* d_tab = mf.d_tab[si];
+            std::memcpy(h_tab, r.rows.data(), (size_t)m * 4);
+            std::memcpy(h_tab + m, r.lens.data(), (size_t)m * 4);
+            hipError_t e = hipMemcpyAsync(s.d_arena, s.h_stage, r.bytes, hipMemcpyHostToDevice, s.stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_tab, h_tab, (size_t)m * 8, hipMemcpyHostToDevice, s.stream);
+            if (e == hipSuccess && have_prev) e = hipStreamWaitEvent(s.stream, mf.chain, 0);
+#ifdef VX_TEST_HOOKS
+            if (e == hipSuccess && c->fail_launch_after >= 0 && c->fail_launch_after-- == 0) {
+                rc = fail(VX_EDEVICE, std::string(who) + ": injected launch failure (vx_tuning_fail_launch_after)");
+                break;
+            }
+#endif
+            if (e == hipSuccess) e = vx::launch_merkle_blocks(s.d_arena, d_tab, d_tab + m, m, mf.d_window, s.stream);
+            for (const vx_merkle::Nodes& g : r.nodes) {
+                if (e != hipSuccess) break;
+                const uint64_t k = g.first - first;
+                e = vx::launch_merkle_nodes(mf.d_window + (size_t)g.row0 * 32, d_lw + k, g.n, g.log2_width, nullptr,
+                                            d_exp + k * 32, d_match + k, s.stream);
+            }
+            if (e == hipSuccess) e = hipEventRecord(mf.chain, s.stream);
+            if (e == hipSuccess) e = hipEventRecord(s.done, s.stream);
+            if (e != hipSuccess) {
+                rc = hip_fail(e, "vx_merkle_verify_files: enqueue");
+                break;
+            }
+            have_prev = true;
+            live[si] = 1;
+            ++n_rounds;
+            n_bytes += r.file_bytes;
+            copy_bytes += r.bytes;
+            t_last_enqueue = clk::now();
+        }
+        rd.wait();  // error path: no read may still target a stage
+        for (size_t si = 0; si < nslots; ++si)  // ... and no copy may still read one
+            if (c->slots[si].stream && hipStreamSynchronize(c->slots[si].stream) != hipSuccess && !rc)
+                rc = fail(VX_EDEVICE, std::string(who) + ": a round failed on the device");
+        std::vector<uint8_t> verdict(count);
+        if (!rc && hipMemcpy(verdict.data(), d_match, count, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(VX_EDEVICE, std::string(who) + ": verdict download failed");
+        vx_verify_trace& vt = c->last_verify;
+        vt.tail_ms = std::chrono::duration<double, std::milli>(clk::now() - t_last_enqueue).count();
+        vt.read_busy_ms = rd.busy_ns() * 1e-6;
+        vt.read_bytes = rd.bytes_read();
+        vt.direct_bytes = dio.direct_bytes();
+        vt.readers = (uint32_t)rd.threads();
+        vt.rounds = (uint32_t)n_rounds;
+        vt.copy_bytes = copy_bytes;
+        vt.chunk_bytes = (uint64_t)bpr * VX_MERKLE_BLOCK;
+        if (rd.first_start_ns()) {
+            vt.read_span_ms = (rd.last_end_ns() - rd.first_start_ns()) * 1e-6;
+            vt.first_read_ms = (rd.first_end_ns() - t_call) * 1e-6;
+        }
+        if (!rc) {
+            uint64_t mism = 0;
+            for (size_t i = 0; i < count; ++i) {
+                matched_out[i] = verdict[i] && !bad[i] ? 1 : 0;
+                mism += !verdict[i] && !bad[i];  // I/O errors count in io_errors only
+            }
+            c->stats.pieces_completed += count;
+            c->stats.pieces_mismatched += mism;
+            c->stats.bytes_completed += n_bytes;
+            c->stats.batches += n_rounds;
+        }
+    }
+    for (int fd : fds)
+        if (fd >= 0) close(fd);
+    c->last_verify.wall_ms = (vx_files::Readers::now_ns() - t_call) * 1e-6;
+    if (rc) return rc;
+    int64_t nbad = 0;
+    for (uint8_t x : bad) nbad += x;
+    c->stats.io_errors += (uint64_t)nbad;
+    return nbad;
+}
+
+int64_t vx_merkle_verify_files_range(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                                     uint32_t piece_length, const uint8_t* expected, size_t n_pieces, size_t first,
+                                     size_t count, uint8_t* matched_out, uint32_t io_threads) {
+    return merkle_files_impl(c, paths, file_lengths, nfiles, piece_length, expected, n_pieces, first, count,
+                             matched_out, io_threads);
+}
+
+int64_t vx_merkle_verify_files(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                               uint32_t piece_length, const uint8_t* expected, size_t n_pieces, uint8_t* matched_out,
+                               uint32_t io_threads) {
+    return merkle_files_impl(c, paths, file_lengths, nfiles, piece_length, expected, n_pieces, 0, n_pieces,
+                             matched_out, io_threads);
 }
 
 // Host-only cost model of a bulk verify.  One piece is one

@@ -332,9 +332,14 @@ class Runs {
 // is the first piece of the verified range.
 class Readers {
   public:
+    // blocks (the v2 re-verify, vx_merkle_rounds.hpp): every item is a run of
+    // 16 KiB blocks of one file (file >= 0), `piece` the v2 piece of its first
+    // block; fs is not used.  A run that fails is re-read block by block, and a
+    // block that fails marks its own piece (no v2 piece spans files, so the
+    // pieces of a run follow from its file offsets).
     Readers(int n, const std::vector<FileSpan>& fs, const std::vector<int>& fds, uint32_t piece_length,
-            uint8_t* bad, uint64_t first = 0, const DirectIo* dio = nullptr)
-        : fs_(fs), fds_(fds), pl_(piece_length), bad_(bad), first_(first), dio_(dio) {
+            uint8_t* bad, uint64_t first = 0, const DirectIo* dio = nullptr, bool blocks = false)
+        : fs_(fs), fds_(fds), pl_(piece_length), bad_(bad), first_(first), dio_(dio), blocks_(blocks) {
         for (int t = 0; t < n; ++t) {
             try {
                 th_.emplace_back([this] { loop(); });
@@ -443,6 +448,15 @@ class Readers {
                                  : read_full(fds_[it.file], it.dst, it.file_off, (int64_t)it.len);
             if (ok) return;
         }
+        if (blocks_) {
+            constexpr uint64_t kLeaf = 16384;
+            for (uint64_t at = 0; at < it.len; at += kLeaf) {
+                const int64_t off = it.file_off + (int64_t)at;
+                if (!read_full(fds_[it.file], it.dst + at, off, (int64_t)std::min<uint64_t>(kLeaf, it.len - at)))
+                    mark_bad(it.piece + (uint64_t)(off / pl_) - (uint64_t)(it.file_off / pl_));
+            }
+            return;
+        }
         if (it.file < 0) {
             if (!read_range(fs_, fds_, pl_, it, segs, dio_)) mark_bad(it.piece);
             return;
@@ -492,6 +506,7 @@ class Readers {
     uint8_t* bad_;
     const uint64_t first_;
     const DirectIo* dio_;
+    const bool blocks_;
     std::vector<std::thread> th_;
     std::mutex mu_;
     std::condition_variable cv_, done_cv_;

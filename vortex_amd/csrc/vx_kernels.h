@@ -93,6 +93,14 @@ hipError_t launch_merkle_uniform(const uint8_t* base, uint64_t stride, uint32_t 
 hipError_t launch_merkle_ragged(const uint8_t* base, const uint64_t* offsets, const uint32_t* lens,
                                 const uint8_t* log2w, uint32_t n, uint32_t log2_width, uint8_t* leaves,
                                 uint8_t* roots, const uint8_t* expected, uint8_t* matched, hipStream_t stream);
+// The two halves on their own (the re-verify from disk): the block kernel
+// hashes stage block b (lens[b] <= 16384 bytes at stage + b*16384) into leaf
+// row rows[b] (0xFFFFFFFF: none; lens[b] == 0: the zero hash, nothing read);
+// the node kernels reduce n pieces' rows that are already in leaves.
+hipError_t launch_merkle_blocks(const uint8_t* stage, const uint32_t* rows, const uint32_t* lens, uint32_t n_blocks,
+                                uint8_t* leaves, hipStream_t stream);
+hipError_t launch_merkle_nodes(const uint8_t* leaves, const uint8_t* log2w, uint32_t n, uint32_t log2_width,
+                               uint8_t* roots, const uint8_t* expected, uint8_t* matched, hipStream_t stream);
 // Root of a layer of n >= 1 hashes; pads[k] = the pad hash of the layer's
 // height + k (one per level to the root); work: 32*n bytes.
 hipError_t launch_merkle_root(const uint8_t* layer, uint32_t n, uint8_t* work, uint8_t* root,

@@ -298,6 +298,85 @@ def merkle_ragged(data: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor,
     return roots, leaves, matched
 
 
+SKIP_ROW = 0xFFFFFFFF  # merkle_blocks: a block that stores no leaf row
+
+
+def merkle_blocks(stage: torch.Tensor, rows: torch.Tensor, lens: torch.Tensor, leaves: torch.Tensor,
+                  stream: Optional[torch.cuda.Stream] = None, validate: bool = True) -> torch.Tensor:
+    """Hash 16 KiB stage blocks into leaf rows (vx_merkle_device_blocks): block
+    b is stage[b*16384 : b*16384 + lens[b]] and its SHA-256 goes to row rows[b]
+    of `leaves` ([R,32] uint8).  rows: int64 or int32 device tensor holding
+    values 0..R-1 or SKIP_ROW (the block stores nothing); lens: int32, 0..16384;
+    a block of length 0 stores the zero hash and is never read, so it may lie
+    past the end of `stage`.  validate (default): rows in range, lengths in
+    range and every read block inside `stage`, checked on the device with one
+    copy back (a sync).  Returns `leaves`.  Enqueue-only otherwise."""
+    _req(stage, "stage")
+    _req(leaves, "leaves")
+    _req(lens, "lens", torch.int32)
+    if rows.dtype not in (torch.int64, torch.int32) or not rows.is_cuda or not rows.is_contiguous():
+        raise ValueError("rows must be a contiguous int64 or int32 device tensor")
+    n = rows.numel()
+    if lens.numel() != n:
+        raise ValueError("rows and lens differ in length")
+    dev = stage.device
+    for name, t in (("rows", rows), ("lens", lens), ("leaves", leaves)):
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, stage on {dev}")
+    if leaves.numel() % 32:
+        raise ValueError("leaves must hold whole 32-byte rows")
+    need64 = rows.dtype != torch.int32 or (validate and n)  # (an int32 table goes to the kernel as it is)
+    r64 = rows.to(torch.int64) & 0xFFFFFFFF if need64 else None
+    if validate and n:
+        live = r64.ne(SKIP_ROW)
+        read = live & lens.gt(0)
+        ends = torch.arange(n, device=dev, dtype=torch.int64) * 16384 + lens.to(torch.int64)
+        stats = torch.stack([
+            torch.where(live, r64, torch.zeros_like(r64)).max(),
+            lens.min().to(torch.int64),
+            lens.max().to(torch.int64),
+            torch.where(read, ends, torch.zeros_like(ends)).max(),
+        ]).cpu().tolist()
+        if stats[0] >= leaves.numel() // 32:
+            raise ValueError(f"merkle_blocks: row {stats[0]} is outside leaves ({leaves.numel() // 32} rows)")
+        if stats[1] < 0 or stats[2] > 16384:
+            raise ValueError("merkle_blocks: a block length is outside 0..16384")
+        if stats[3] > stage.numel():
+            raise ValueError(f"merkle_blocks: a block ends at byte {stats[3]}, past the stage ({stage.numel()} bytes)")
+    rows32 = r64.to(torch.int32) if rows.dtype != torch.int32 else rows  # (wraps SKIP_ROW to -1: the same bits)
+    if stream is not None:
+        rows32.record_stream(stream)
+    rc = lib().vx_merkle_device_blocks(stage.data_ptr(), rows32.data_ptr(), lens.data_ptr(), n, leaves.data_ptr(),
+                                       _stream_ptr(stream, dev))
+    check(rc, "vx_merkle_device_blocks")
+    return leaves
+
+
+def merkle_nodes(leaves: torch.Tensor, n: int, log2_width: int, log2w: Optional[torch.Tensor] = None,
+                 expected: Optional[torch.Tensor] = None, roots: Optional[torch.Tensor] = None,
+                 matched: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None):
+    """Reduce leaf rows already on the device to the roots of n pieces
+    (vx_merkle_device_nodes): piece i's rows start at row i << log2_width and
+    its tree has 2^log2w[i] slots (None: log2_width).  Returns (roots [n,32],
+    matched [n] or None).  Enqueue-only."""
+    _req(leaves, "leaves")
+    dev = leaves.device
+    if log2w is not None:
+        _req(log2w, "log2w")
+        if log2w.numel() != n or log2w.device != dev:
+            raise ValueError("log2w must hold n widths on the leaves' device")
+        if n and int(log2w.max()) > log2_width:
+            raise ValueError("merkle_nodes: a log2w is above log2_width")
+    leaves, roots, matched = _merkle_outputs(n, log2_width, dev, expected, leaves, roots, matched)
+    rc = lib().vx_merkle_device_nodes(leaves.data_ptr(), log2w.data_ptr() if log2w is not None else None, n,
+                                      log2_width, roots.data_ptr(),
+                                      expected.data_ptr() if expected is not None else None,
+                                      matched.data_ptr() if matched is not None else None,
+                                      _stream_ptr(stream, dev))
+    check(rc, "vx_merkle_device_nodes")
+    return roots, matched
+
+
 def merkle_root(layer: torch.Tensor, height: int = 0, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
     """Root of a layer of hashes ([n,32] uint8) standing `height` levels above
     the leaves, padded to a power of two with pad hashes

@@ -349,6 +349,33 @@ class HashPool:
         raw = roots.raw
         return [bool(b) for b in matched.raw[:n]], [raw[32 * i: 32 * i + 32] for i in range(n)]
 
+    def verify_merkle_files(self, paths: Sequence[str], file_lengths: Sequence[int], piece_length: int,
+                            expected: bytes, io_threads: int = 0, first: int = 0,
+                            count: int | None = None) -> tuple[list[bool], int]:
+        """BitTorrent v2 (BEP 52) re-verify from disk (vx_merkle_verify_files):
+        the pieces of every file, numbered file by file
+        (merkle.torrent_pieces), read in rounds of 16 KiB blocks and verified
+        against `expected` (n*32 bytes: each file's `piece layers` entry, or
+        its `pieces root` for a file of at most piece_length bytes).  The
+        piece length is not bounded by the pool's.  Returns (verdicts, pieces
+        with I/O errors); first/count restrict the call to pieces
+        [first, first+count) and the verdicts then cover that range."""
+        n = len(expected) // 32
+        if count is None:
+            count = n - first
+        arr = (ctypes.c_char_p * max(1, len(paths)))(*[os.fsencode(p) for p in paths])
+        lens = (ctypes.c_uint64 * max(1, len(file_lengths)))(*file_lengths)
+        exp = ctypes.create_string_buffer(bytes(expected), max(1, len(expected)))
+        out = ctypes.create_string_buffer(max(1, count))
+        if first == 0 and count == n:
+            rc = self.lib.vx_merkle_verify_files(self._h, arr, lens, len(paths), piece_length, exp, n, out,
+                                                 io_threads)
+        else:
+            rc = self.lib.vx_merkle_verify_files_range(self._h, arr, lens, len(paths), piece_length, exp, n, first,
+                                                       count, out, io_threads)
+        bad = check(rc, "vx_merkle_verify_files", self.lib)
+        return [bool(b) for b in out.raw[:count]], int(bad)
+
 
 def _verify_files(pool: "HashPool", paths: Sequence[str], file_lengths: Sequence[int], piece_length: int,
                   expected: bytes, io_threads: int = 0, first: int = 0,

@@ -46,6 +46,26 @@ def file_pieces(file_length: int, piece_length: int) -> tuple[list[int], list[in
     return lens, [full] * n
 
 
+def torrent_pieces(file_lengths, piece_length: int) -> tuple[list[int], list[int], list[int], list[int]]:
+    """(lens, log2w, file_index, file_offset) of every piece of a torrent:
+    :func:`file_pieces` file after file, in the order given.  Every file starts
+    its own pieces and no piece spans files; an empty file has none.  This is
+    the numbering ``HashPool.verify_merkle_files`` and its ``expected`` table
+    use: piece i is file_lengths[file_index[i]] bytes
+    [file_offset[i], file_offset[i] + lens[i])."""
+    lens: list[int] = []
+    log2w: list[int] = []
+    file_index: list[int] = []
+    file_offset: list[int] = []
+    for f, length in enumerate(file_lengths):
+        fl, fw = file_pieces(int(length), piece_length)
+        lens += fl
+        log2w += fw
+        file_index += [f] * len(fl)
+        file_offset += [k * piece_length for k in range(len(fl))]
+    return lens, log2w, file_index, file_offset
+
+
 def pad_hash(height: int) -> bytes:
     """pad(0) = 32 zero bytes; pad(h) = SHA-256(pad(h-1) || pad(h-1)): the root
     of an all-zero subtree of 2^height leaves (vx_merkle_pad_hash)."""
