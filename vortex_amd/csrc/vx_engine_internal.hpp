@@ -1,0 +1,368 @@
+// vx_engine_internal.hpp — what every host unit of the engine shares (DESIGN.md
+// "Host engine"): error reporting, the slot and context structs (one layout
+// with and without VX_TEST_HOOKS), the slot primitives of vx_engine.hip.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <fcntl.h>
+#include <sched.h>
+#include <sys/mman.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <cctype>
+#include <chrono>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <deque>
+#include <functional>
+#include <map>
+#include <unordered_map>
+#include <numeric>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "vx_files.hpp"
+#include "vx_hash.h"
+#include "vx_kernels.h"
+#include "vx_merkle_rounds.hpp"
+#include "vx_synth.h"
+#include "vx_tuning.h"
+
+namespace vxe {
+
+// the library's one error text per thread (vx_engine.hip): fail() writes it, vx_last_error reads it
+extern thread_local std::string g_err;
+int fail(int code, const std::string& msg);
+int hip_fail(hipError_t e, const char* what);
+
+#define VX_HIP(call)                                    \
+    do {                                                  \
+        hipError_t _e = (call);                           \
+        if (_e != hipSuccess) return hip_fail(_e, #call); \
+    } while (0)
+
+constexpr uint64_t kAlign = 256;
+
+inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
+
+struct Run {
+    uint64_t lo, hi;  // staged byte range [lo, hi) of the arena
+};
+
+struct DirectRun {
+    const uint8_t* host;  // registered (pinned) source of arena bytes [lo, hi)
+    uint64_t lo, hi;
+};
+
+struct StageCopy {
+    const uint8_t* src;  // unregistered caller bytes for stage [off, off + len)
+    uint64_t off;
+    uint32_t len;
+};
+
+struct Slot {
+    hipStream_t stream = nullptr;
+    hipEvent_t done = nullptr;
+    hipEvent_t copied = nullptr;  // this slot's H2D finished on the copy stream
+    uint64_t arena_cap = 0;
+    uint32_t cap = 0;  // pieces
+    uint8_t* d_arena = nullptr;
+    uint8_t* h_stage = nullptr;
+    uint64_t stage_map = 0;  // > 0: h_stage is a registered mmap of this many bytes (alloc_stage)
+    // pinned metadata block: offsets | lens | expected | digests | matched
+    uint8_t* h_meta = nullptr;
+    uint8_t* d_meta = nullptr;
+    uint64_t* h_offsets = nullptr;
+    uint32_t* h_lens = nullptr;
+    uint8_t* h_expected = nullptr;
+    uint8_t* h_digests = nullptr;
+    uint8_t* h_matched = nullptr;
+    uint32_t* h_pidx = nullptr;  // piece-table rows (vx_submit_piece) / piece ids (chunks)
+    uint32_t* d_pidx = nullptr;
+    uint64_t* h_poff = nullptr;  // chunked re-verify: chunk offset within its piece
+    uint64_t* d_poff = nullptr;
+    uint64_t* h_tlen = nullptr;  // chunked re-verify: the piece's total length
+    uint64_t* d_tlen = nullptr;
+    uint64_t* h_src = nullptr;   // gather: device-mapped source of piece i (0 = not gathered)
+    uint64_t* d_src = nullptr;
+    uint32_t* h_tfirst = nullptr;  // gather: piece i owns tiles [tfirst[i], tfirst[i+1])
+    uint32_t* d_tfirst = nullptr;
+    uint32_t gtiles = 0;           // gather tiles of this batch
+    uint64_t* d_offsets = nullptr;
+    uint32_t* d_lens = nullptr;
+    uint8_t* d_expected = nullptr;
+    uint8_t* d_digests = nullptr;
+    uint8_t* d_matched = nullptr;
+    std::vector<uint64_t> tags;
+    std::vector<Run> runs;
+    std::vector<DirectRun> druns;
+    std::vector<StageCopy> staged;  // host batches: stage copies deferred to launch
+    uint64_t staged_bytes = 0;
+    uint32_t n = 0;
+    uint64_t bytes = 0;
+    bool uniform = true;
+    bool has_expected = false;
+    bool use_table = false;  // expected digests come from the device piece table
+    bool all_mapped = true;  // every non-empty piece is registered and 16-byte aligned (zero-copy candidate)
+    enum State { FREE, FILLING, INFLIGHT } state = FREE;
+    uint64_t seq = 0;
+    std::chrono::steady_clock::time_point t_open{};  // first piece queued (vx_stats batch latency)
+};
+
+}  // namespace vxe
+
+struct vx_ctx {
+    // Everything a caller chooses comes in here (vx_config, ABI 2): the
+    // engine reads no environment variables.
+    vx_config cfg{};
+    std::vector<vxe::Slot> slots;
+    // H2D copies are serialised across slots in launch order, so PCIe moves
+    // one batch at a time at full rate and batch k's kernel starts as soon as
+    // its own bytes are in, while batch k+1 copies (chain_h2d).  (Copies
+    // racing on all slot streams share PCIe and delay every kernel.)
+    int last_launched = -1;  // slot whose H2D was enqueued last
+    // Per-piece device rows of the chunk paths (state | expected | digest |
+    // verdict), kept across calls and grown on demand: allocating them per
+    // call cost ~1 ms of a 40 ms e2e batch.
+    uint8_t* d_chunk_rows = nullptr;
+    uint64_t chunk_rows_cap = 0;
+    hipEvent_t chunk_prev = nullptr;
+    // Device-resident `pieces` table (vx_set_piece_table).
+    uint8_t* d_table = nullptr;
+    uint32_t n_table = 0;
+    int filling = -1;
+    // vx_flush found every other slot in flight and left the filling slot
+    // open; vx_poll launches it once a slot frees.
+    bool flush_pending = false;
+    bool bulk = false;  // inside vx_*_batch: slots fill to capacity, not to batch_pieces
+    std::deque<vx_completion> done;
+    struct Reg {
+        size_t len;
+        uint8_t* dev;  // device mapping of the range (hipHostGetDevicePointer)
+    };
+    std::map<uintptr_t, Reg> registered;
+    // The same ranges keyed by start address: vortex submits each piece from
+    // the start of its own pool mmap (buf_pool.rs:92-98), so most lookups are
+    // one hash probe instead of a tree walk.  16 KiB pieces from 1,024
+    // separately registered buffers: 29.7 -> 35.7 GiB/s.
+    std::unordered_map<uintptr_t, Reg> registered_at;
+    uint64_t pending = 0;
+    uint64_t seq = 0;
+    int sticky = 0;
+    // Fault injection, used only in the test build libvortex_amd_tuning.so
+    // (VX_TEST_HOOKS; always members, so every unit agrees on the layout).
+    // vx_tuning_fail_submit_after: the submit after this many more succeeds
+    // fails with VX_ENOMEM, the way a failed pinned-stage allocation does;
+    // < 0 = off.
+    int64_t fail_submit_after = -1;
+    // vx_tuning_fail_launch_after: the launch after this many more fails as a
+    // device error would, turning the context sticky; < 0 = off.
+    int64_t fail_launch_after = -1;
+    vx_stats stats{};  // vx_get_stats (observability counters)
+    // harvest() counts mismatches unless the caller overrides verdicts after
+    // it (the file re-verify: a piece with an I/O error is counted in
+    // io_errors only, FileVerify::consume counts the final verdicts)
+    bool harvest_counts_mismatches = true;
+    // vx_last_verify: the last file re-verify's time budget, and the timing
+    // events around its chunk rounds' data copies (reused across calls)
+    vx_verify_trace last_verify{};
+    std::vector<hipEvent_t> copy_ev;
+    std::vector<vx_verify_round> last_rounds;  // vx_last_verify_rounds
+    // the last split call's decisions, one per round formed (vx_tuning_last_split)
+    struct SplitDecision {
+        double t_ms, pool_rate, engine_rate, block_ns, t_engine_ms, t_pool_ms;
+        uint64_t unclaimed, group, lanes, pool_done;
+        uint32_t mode, measured;
+        double lag_ms;  // the learned lag in t_engine_ms
+    };
+    std::vector<SplitDecision> last_split;
+    // What earlier split calls measured, the next call's cold start: the
+    // engine's copy intake
+    // (B/s, first copy start to last copy end), the kernel's chain per block,
+    // and the pool's bytes/s per thread beside the engine (0 = none yet).
+    // Each keeps the last kLearn calls' samples: the next call uses their
+    // median (split_learn 1, default), so one call slowed by a host stall
+    // does not move the next call's first group — and for the intake their
+    // largest: a stall slows the pool as much as the engine's reads, and the
+    // pool's side starts from its own rate alone, so the engine's starts from
+    // its unstalled one too.  split_learn 0 (test build) uses the running mean
+    // instead (each call weighted 1/2).
+    struct Learned {
+        static constexpr uint32_t kLearn = 5;
+        double ring[kLearn] = {}, mean = 0;
+        uint32_t n = 0;
+        void add(double x) {
+            mean = n ? 0.5 * (mean + x) : x;
+            ring[n++ % kLearn] = x;
+        }
+        bool any() const { return n > 0; }
+        double top() const { return *std::max_element(ring, ring + std::min(n, kLearn)); }
+        double get(int median) const {
+            if (!median) return mean;
+            double v[kLearn];
+            const uint32_t k = std::min(n, kLearn);
+            std::copy(ring, ring + k, v);
+            std::sort(v, v + k);
+            return k % 2 ? v[k / 2] : 0.5 * (v[k / 2 - 1] + v[k / 2]);
+        }
+    };
+    // [0]: calls over page-cached data, [1]: over uncached data (O_DIRECT
+    // reads; the disk, not PCIe, feeds the engine): one regime's figures
+    // would mislead the other's first group.
+    Learned split_rin[2], split_bns[2], split_pool_thread_rate[2];
+    int split_learn = 1;
+    // How much later the engine's last kernel ended than the first group's
+    // T_engine said, less the same for the pool's last verdict and T_pool, in
+    // calls where the first group was the engine's only one (the readers'
+    // start-up and the kernels trailing the copies, which the round model
+    // leaves out), kept the same way; the next first group's T_engine adds
+    // it.
+    Learned split_lag[2];
+    int split_lag_on = 1;  // 0: learned, not applied (vx_tuning_split_rules)
+    // The file re-verify's chunk rounds put every H2D on this one stream (high
+    // priority: its own hardware queue) and only kernels on the slot streams,
+    // so no copy ever sits behind a kernel.  Created on first
+    // use.  verify_copy_stream = 0 (test build only) restores the slot-stream
+    // copies for A/B.
+    hipStream_t copy_stream = nullptr;
+    int verify_copy_stream = 1;
+    // How pinned stages are allocated (alloc_stage): 1 = 2 MiB-aligned mmap
+    // with transparent huge pages, then hipHostRegister; 0 = hipHostMalloc
+    // (vx_tuning_stage_huge, test build).  Huge pages: warm re-verify 39.1 ->
+    // 45.2 GiB/s (its H2D copies 44-47 -> 49-50.5), cold 10.9 -> 14.2, median
+    // of 7-9 alternating calls on one box.
+    int stage_huge = 1;
+    // The split's rules for pieces of one chunk (vx_tuning_split_rules, test
+    // build): one_round 1 lets their groups keep claiming while the rates
+    // are cold and skips the tenth rule (0: the multi-round rules; 2: as 1,
+    // reading piece by piece instead of in runs);
+    // round_cap > 0 caps their rounds' bytes (at no fewer than 1,024 lanes),
+    // 0: the slot's stage.
+    int split_one_round = 1;
+    uint64_t split_round_cap = 64ull << 20;
+    hipEvent_t anchor_ev = nullptr;            // maps the rounds' GPU times onto the host clock
+    // vx_merkle_verify_batch: per slot, a device block (metadata in | results
+    // out | leaf rows) and its pinned host mirror (in | out), allocated on the
+    // first call; merkle_rows = leaf rows (and pieces) one round holds.
+    struct MerkleBufs {
+        uint8_t* d = nullptr;
+        uint8_t* h = nullptr;
+    };
+    std::vector<MerkleBufs> merkle;
+    uint32_t merkle_rows = 0;
+    // vx_merkle_verify_files: the leaf-row window, per slot the pinned and
+    // device rows | lens tables of a round, the per-call device rows
+    // (expected | verdict | log2w per piece) and the event that orders one
+    // round's kernels after the last round's; all kept across calls and grown
+    // on demand.
+    struct MerkleFiles {
+        uint8_t* d_window = nullptr;
+        uint64_t window_rows = 0;
+        std::vector<uint32_t*> h_tab, d_tab;
+        uint64_t tab_entries = 0;
+        uint8_t* d_call = nullptr;
+        uint64_t call_cap = 0;
+        hipEvent_t chain = nullptr;
+    } mfiles;
+    uint64_t verify_t0_ns = 0;                // the running re-verify call's start (steady clock)
+};
+
+namespace vxe {
+
+// The GPU's per-block chain time on the split kernels and the PCIe rate: the
+// cost model's hardware figures (vx_plan_verify), and the
+// split's cold-start guesses before it has measured its own.
+constexpr double kChainBlock = 0.76e-6, kPcieRate = 52.0 * (1ull << 30);
+
+// Slot primitives (vx_engine.hip).
+int set_device(const vx_ctx* c);
+bool is_registered(const vx_ctx* c, const void* p, size_t len, const uint8_t** dev = nullptr);
+unsigned usable_cpus();
+int ensure_stage(const vx_ctx* c, Slot& s);
+void reset_fill(Slot& s);
+int chain_h2d(vx_ctx* c, int si);
+void mark_launched(vx_ctx* c, int si);
+int launch_slot(vx_ctx* c, int si);
+int reap(vx_ctx* c, bool block_oldest);
+int submit_impl(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, const uint8_t* expected,
+                int64_t piece_row = -1);
+void abandon_batch(vx_ctx* c);
+void release_filling_slots(vx_ctx* c);   // every FILLING slot (reserved, never launched) back to FREE
+void wait_and_free_inflight(vx_ctx* c);  // wait for every INFLIGHT slot, then free them unharvested
+// A bulk call's guard: nothing pending (VX_EBUSY), not sticky, an empty filling
+// slot handed back and, with need_idle, no slot in use ("a batch is in flight").
+int begin_bulk_call(vx_ctx* c, const std::string& who, bool need_idle);
+
+// A slot that is free now, after polling completions without blocking (on_reap
+// runs after the poll); -1 in *si when there is none.
+template <class F>
+int try_free_slot(vx_ctx* c, int* si, F&& on_reap) {
+    *si = -1;
+    const int rc = reap(c, false);
+    on_reap();
+    if (rc) return rc;
+    for (int k = 0; k < (int)c->slots.size() && *si < 0; ++k)
+        if (c->slots[k].state == Slot::FREE) *si = k;
+    return 0;
+}
+// A free slot, reaping the oldest in-flight one when none is; on_reap runs
+// after every blocking reap.  none: the error when nothing is in flight either.
+template <class F>
+int free_slot(vx_ctx* c, const char* none, F&& on_reap) {
+    for (;;) {
+        bool inflight = false;
+        for (int k = 0; k < (int)c->slots.size(); ++k) {
+            if (c->slots[k].state == Slot::FREE) return k;
+            inflight |= c->slots[k].state == Slot::INFLIGHT;
+        }
+        if (!inflight) return fail(VX_EDEVICE, none);
+        int rc = reap(c, true);
+        on_reap();
+        if (rc) return rc;
+    }
+}
+// free_slot (block) or try_free_slot into *si; the error, or 0 (*si < 0: none free now).
+template <class F>
+int take_slot(vx_ctx* c, bool block, const char* none, int* si, F&& on_reap) {
+    if (!block) return try_free_slot(c, si, on_reap);
+    *si = free_slot(c, none, on_reap);
+    return *si < 0 ? *si : 0;
+}
+
+// The end of a file re-verify call (SHA-1 or merkle): what vx_last_verify
+// reports of its readers; then the files closed, the wall time, and the
+// call's result: rc, or the count of pieces with I/O errors (into vx_stats).
+inline void trace_reads(vx_verify_trace& vt, vx_files::Readers& rd, const vx_files::DirectIo& dio, uint64_t t_call) {
+    vt.read_busy_ms = rd.busy_ns() * 1e-6;
+    vt.read_bytes = rd.bytes_read();
+    vt.direct_bytes = dio.direct_bytes();
+    vt.readers = (uint32_t)rd.threads();
+    if (rd.first_start_ns()) {
+        vt.read_span_ms = (rd.last_end_ns() - rd.first_start_ns()) * 1e-6;
+        vt.first_read_ms = (rd.first_end_ns() - t_call) * 1e-6;
+    }
+}
+inline int64_t end_files_call(vx_ctx* c, const std::vector<int>& fds, const std::vector<uint8_t>& bad,
+                              uint64_t t_call, int rc) {
+    for (int fd : fds)
+        if (fd >= 0) close(fd);
+    c->last_verify.wall_ms = (vx_files::Readers::now_ns() - t_call) * 1e-6;
+    if (rc) return rc;
+    int64_t nbad = 0;
+    for (uint8_t x : bad) nbad += x;
+    c->stats.io_errors += (uint64_t)nbad;
+    return nbad;
+}
+void free_merkle_files(vx_ctx* c);  // vx_merkle.hip: vx_merkle_verify_files' buffers, not its event
+// vx_reverify.hip, the _multi calls.  check_contexts: no NULL, no duplicate.
+// fan_out: fn(k) for k in [0, nctx), one host thread per context (context 0,
+// and any whose thread could not start, on the caller's); the sum of the
+// results, or the first failing context's code, its error prefixed "context k: ".
+int check_contexts(vx_ctx* const* ctxs, size_t nctx, const char* who);
+int64_t fan_out(size_t nctx, const std::function<int64_t(size_t)>& fn);
+
+}  // namespace vxe

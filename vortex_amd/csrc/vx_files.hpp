@@ -1,5 +1,5 @@
 // vx_files.hpp — host-side pieces of the bulk re-verify from disk
-// (vx_verify_files in vx_engine.hip): the torrent file layout, each piece's
+// (vx_verify_files in vx_reverify.hip): the torrent file layout, each piece's
 // file segments, and a pool of pread threads.
 //
 // Replaces State::from_metadata_and_root's
@@ -9,7 +9,7 @@
 // FileStore::check_piece_hash_sync (bittorrent/src/file_store.rs:228-303) and
 // the file layout of FileStore::new (file_store.rs:126-160).
 //
-// Pipeline (vx_engine.hip): the readers pread the next slot's pieces straight
+// Pipeline (vx_reverify.hip): the readers pread the next slot's pieces straight
 // into that slot's pinned stage while the GPU copies and hashes the slots
 // already launched; a piece's segments land back to back at its arena offset.
 #include <fcntl.h>

@@ -1,0 +1,580 @@
+// vx_merkle.hip — the BitTorrent v2 merkle entries of vx_hash.h (kernels in
+// sha256_kernels.hip): vx_merkle_device_*, _verify_batch, _verify_files.
+#include "vx_engine_internal.hpp"
+
+using namespace vxe;
+
+// The buffers of vx_merkle_verify_files (not its event).
+void vxe::free_merkle_files(vx_ctx* c) {
+    vx_ctx::MerkleFiles& m = c->mfiles;
+    if (m.d_window) (void)hipFree(m.d_window);
+    if (m.d_call) (void)hipFree(m.d_call);
+    for (uint32_t* p : m.h_tab)
+        if (p) (void)hipHostFree(p);
+    for (uint32_t* p : m.d_tab)
+        if (p) (void)hipFree(p);
+    hipEvent_t chain = m.chain;
+    m = vx_ctx::MerkleFiles{};
+    m.chain = chain;
+}
+
+extern "C" {
+
+// SHA-256(a || b) of two 32-byte hashes on the host: what vx_merkle_pad_hash needs.
+static void host_sha256_pair(const uint8_t* a, const uint8_t* b, uint8_t* out) {
+    static const uint32_t K[64] = {
+        0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u,
+        0xd807aa98u, 0x12835b01u, 0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u,
+        0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, 0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau,
+        0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u, 0x06ca6351u, 0x14292967u,
+        0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u,
+        0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u,
+        0x19a4c116u, 0x1e376c08u, 0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u,
+        0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u, 0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
+    uint32_t h[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
+                     0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
+    auto rotr = [](uint32_t x, int n) { return (x >> n) | (x << (32 - n)); };
+    for (int blk = 0; blk < 2; ++blk) {  // the 64 message bytes, then the padding block
+        uint32_t w[64] = {};
+        if (blk == 0) {
+            for (int k = 0; k < 16; ++k) {
+                const uint8_t* p = (k < 8 ? a : b) + 4 * (k & 7);
+                w[k] = (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3];
+            }
+        } else {
+            w[0] = 0x80000000u;
+            w[15] = 512;
+        }
+        for (int t = 16; t < 64; ++t)
+            w[t] = w[t - 16] + (rotr(w[t - 15], 7) ^ rotr(w[t - 15], 18) ^ (w[t - 15] >> 3)) + w[t - 7] +
+                   (rotr(w[t - 2], 17) ^ rotr(w[t - 2], 19) ^ (w[t - 2] >> 10));
+        uint32_t s[8];
+        std::copy(h, h + 8, s);
+        for (int t = 0; t < 64; ++t) {
+            const uint32_t t1 = s[7] + (rotr(s[4], 6) ^ rotr(s[4], 11) ^ rotr(s[4], 25)) +
+                                ((s[4] & s[5]) ^ (~s[4] & s[6])) + K[t] + w[t];
+            const uint32_t t2 = (rotr(s[0], 2) ^ rotr(s[0], 13) ^ rotr(s[0], 22)) +
+                                ((s[0] & s[1]) ^ (s[0] & s[2]) ^ (s[1] & s[2]));
+            for (int k = 7; k > 0; --k) s[k] = s[k - 1];
+            s[4] += t1;
+            s[0] = t1 + t2;
+        }
+        for (int k = 0; k < 8; ++k) h[k] += s[k];
+    }
+    for (int k = 0; k < 8; ++k) {
+        out[4 * k] = (uint8_t)(h[k] >> 24);
+        out[4 * k + 1] = (uint8_t)(h[k] >> 16);
+        out[4 * k + 2] = (uint8_t)(h[k] >> 8);
+        out[4 * k + 3] = (uint8_t)h[k];
+    }
+}
+
+constexpr uint32_t kMaxPadHeight = 128;
+
+int vx_merkle_pad_hash(uint32_t height, uint8_t* out) {
+    if (!out) return fail(VX_EINVAL, "vx_merkle_pad_hash: NULL out");
+    if (height > kMaxPadHeight) return fail(VX_EINVAL, "vx_merkle_pad_hash: height > 128");
+    uint8_t cur[32] = {};
+    for (uint32_t h = 0; h < height; ++h) {
+        uint8_t next[32];
+        host_sha256_pair(cur, cur, next);
+        std::memcpy(cur, next, 32);
+    }
+    std::memcpy(out, cur, 32);
+    return 0;
+}
+
+// What both device entries can check on the host.
+static int merkle_args(const char* who, const void* d_base, const void* d_leaves, uint32_t n, uint32_t log2_width) {
+    const std::string w(who);
+    if (!d_base || !d_leaves) return fail(VX_EINVAL, w + ": NULL d_base or d_leaves");
+    if (reinterpret_cast<uintptr_t>(d_base) & 15) return fail(VX_EINVAL, w + ": base must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_leaves) & 15) return fail(VX_EINVAL, w + ": d_leaves must be 16-byte aligned");
+    if (log2_width > VX_MERKLE_MAX_LOG2_WIDTH) return fail(VX_EINVAL, w + ": log2_width > 17");
+    if (((uint64_t)n << log2_width) >> 32) return fail(VX_EINVAL, w + ": n << log2_width does not fit 32 bits");
+    return 0;
+}
+
+int vx_merkle_device_uniform(const void* d_base, uint64_t stride, uint32_t len, uint32_t last_len, uint32_t n,
+                             uint32_t log2_width, void* d_leaves, void* d_roots, const void* d_expected,
+                             void* d_matched, void* stream) {
+    if (n == 0) return 0;
+    int rc = merkle_args("vx_merkle_device_uniform", d_base, d_leaves, n, log2_width);
+    if (rc) return rc;
+    if (stride & 15) return fail(VX_EINVAL, "vx_merkle_device_uniform: stride must be a multiple of 16");
+    if (stride < len) return fail(VX_EINVAL, "vx_merkle_device_uniform: stride < len");
+    if (last_len == 0 || last_len > len) return fail(VX_EINVAL, "vx_merkle_device_uniform: last_len outside (0, len]");
+    if (len > (uint64_t)VX_MERKLE_BLOCK << log2_width)
+        return fail(VX_EINVAL, "vx_merkle_device_uniform: len > 16384 << log2_width");
+    if ((reinterpret_cast<uintptr_t>(d_roots) & 15) || (reinterpret_cast<uintptr_t>(d_expected) & 3))
+        return fail(VX_EINVAL, "vx_merkle_device_uniform: d_roots must be 16-byte and d_expected 4-byte aligned");
+    const bool verdict = d_expected && d_matched;
+    hipError_t e = vx::launch_merkle_uniform(static_cast<const uint8_t*>(d_base), stride, len, last_len, n,
+                                             log2_width, static_cast<uint8_t*>(d_leaves),
+                                             static_cast<uint8_t*>(d_roots),
+                                             verdict ? static_cast<const uint8_t*>(d_expected) : nullptr,
+                                             verdict ? static_cast<uint8_t*>(d_matched) : nullptr,
+                                             static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "merkle uniform kernel launch");
+    return 0;
+}
+
+int vx_merkle_device_ragged(const void* d_base, const uint64_t* d_offsets, const uint32_t* d_lens,
+                            const uint8_t* d_log2w, uint32_t n, uint32_t log2_width, void* d_leaves, void* d_roots,
+                            const void* d_expected, void* d_matched, void* stream) {
+    if (n == 0) return 0;
+    int rc = merkle_args("vx_merkle_device_ragged", d_base, d_leaves, n, log2_width);
+    if (rc) return rc;
+    if (!d_offsets || !d_lens) return fail(VX_EINVAL, "vx_merkle_device_ragged: NULL d_offsets or d_lens");
+    if ((reinterpret_cast<uintptr_t>(d_roots) & 15) || (reinterpret_cast<uintptr_t>(d_expected) & 3))
+        return fail(VX_EINVAL, "vx_merkle_device_ragged: d_roots must be 16-byte and d_expected 4-byte aligned");
+    const bool verdict = d_expected && d_matched;
+    hipError_t e = vx::launch_merkle_ragged(static_cast<const uint8_t*>(d_base), d_offsets, d_lens, d_log2w, n,
+                                            log2_width, static_cast<uint8_t*>(d_leaves),
+                                            static_cast<uint8_t*>(d_roots),
+                                            verdict ? static_cast<const uint8_t*>(d_expected) : nullptr,
+                                            verdict ? static_cast<uint8_t*>(d_matched) : nullptr,
+                                            static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "merkle ragged kernel launch");
+    return 0;
+}
+
+int vx_merkle_device_root(const void* d_layer, uint32_t n, uint32_t height, void* d_work, void* d_root,
+                          void* stream) {
+    if (n == 0) return 0;
+    if (!d_layer || !d_root || (n > 1 && !d_work)) return fail(VX_EINVAL, "vx_merkle_device_root: NULL argument");
+    if ((reinterpret_cast<uintptr_t>(d_layer) | reinterpret_cast<uintptr_t>(d_work) |
+         reinterpret_cast<uintptr_t>(d_root)) & 15)
+        return fail(VX_EINVAL, "vx_merkle_device_root: buffers must be 16-byte aligned");
+    if (height > 64) return fail(VX_EINVAL, "vx_merkle_device_root: height > 64");
+    uint8_t pads[33][32];  // pad(height + k), one per level up to the root of 2^32 rows
+    vx_merkle_pad_hash(height, pads[0]);
+    for (int k = 1; k < 33; ++k) host_sha256_pair(pads[k - 1], pads[k - 1], pads[k]);
+    hipError_t e = vx::launch_merkle_root(static_cast<const uint8_t*>(d_layer), n, static_cast<uint8_t*>(d_work),
+                                          static_cast<uint8_t*>(d_root), pads, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "merkle layer kernel launch");
+    return 0;
+}
+
+// Per-slot buffers of vx_merkle_verify_batch.  A round of m pieces packs its
+// metadata as expected (32m) | offsets (8m) | lens (4m) | log2w (m) and its
+// results as roots (32m) | verdicts (m), so each goes in one copy.
+static int ensure_merkle(vx_ctx* c) {
+    if (!c->merkle.empty()) return 0;
+    const uint64_t rows = align_up(c->slots[0].arena_cap / VX_MERKLE_BLOCK, 16);
+    std::vector<vx_ctx::MerkleBufs> bufs(c->slots.size());
+    int rc = 0;
+    for (auto& m : bufs) {
+        if (hipMalloc(&m.d, rows * (48 + 48 + 32)) != hipSuccess ||
+            hipHostMalloc(&m.h, rows * (48 + 48), hipHostMallocDefault) != hipSuccess) {
+            rc = fail(VX_ENOMEM, "vx_merkle_verify_batch: buffer allocation failed");
+            break;
+        }
+    }
+    if (rc) {
+        for (auto& m : bufs) {
+            if (m.d) (void)hipFree(m.d);
+            if (m.h) (void)hipHostFree(m.h);
+        }
+        return rc;
+    }
+    c->merkle = std::move(bufs);
+    c->merkle_rows = (uint32_t)rows;
+    return 0;
+}
+
+int vx_merkle_verify_batch(vx_ctx* c, const uint8_t* const* ptrs, const uint32_t* lens, const uint8_t* log2w,
+                           size_t n, uint32_t piece_length, const uint8_t* expected, uint8_t* matched_out,
+                           uint8_t* roots_out) {
+    if (!c) return fail(VX_EINVAL, "vx_merkle_verify_batch: NULL context");
+    if (n && (!ptrs || !lens || !expected || !matched_out))
+        return fail(VX_EINVAL, "vx_merkle_verify_batch: NULL ptrs/lens/expected/matched_out");
+    if (piece_length < VX_MERKLE_BLOCK || (piece_length & (piece_length - 1)))
+        return fail(VX_EINVAL, "vx_merkle_verify_batch: piece_length must be a power of two >= 16384");
+    if (piece_length > c->cfg.max_piece_len)
+        return fail(VX_ERANGE, "vx_merkle_verify_batch: piece_length > max_piece_len");
+    uint32_t log2_width = 0;
+    while (((uint32_t)VX_MERKLE_BLOCK << log2_width) < piece_length) ++log2_width;
+    for (size_t i = 0; i < n; ++i) {  // argument errors before anything is queued
+        const uint32_t lw = log2w ? log2w[i] : log2_width;
+        if (lw > log2_width) return fail(VX_EINVAL, "vx_merkle_verify_batch: log2w[i] wider than piece_length");
+        if (lens[i] > (uint64_t)VX_MERKLE_BLOCK << lw)
+            return fail(VX_EINVAL, "vx_merkle_verify_batch: piece longer than its tree (16384 << log2w[i])");
+        if (lens[i] && !ptrs[i]) return fail(VX_EINVAL, "vx_merkle_verify_batch: NULL piece pointer");
+    }
+    int rc = begin_bulk_call(c, "vx_merkle_verify_batch", /*need_idle=*/true);
+    if (rc) return rc;
+    if (n == 0) return 0;
+    rc = set_device(c);
+    if (!rc) rc = ensure_merkle(c);
+    if (rc) return rc;
+
+    const size_t nslots = c->slots.size();
+    const uint32_t max_pieces = c->merkle_rows >> log2_width;  // >= 1: slot_bytes >= max_piece_len >= piece_length
+    struct Round {
+        size_t first = 0;
+        uint32_t m = 0;
+        bool live = false;
+    };
+    std::vector<Round> rounds(nslots);
+    uint64_t n_bad = 0, n_bytes = 0, n_rounds = 0;
+    // Wait for the round slot si carries and take its results.
+    auto harvest_round = [&](size_t si) -> int {
+        Round& r = rounds[si];
+        if (!r.live) return 0;
+        r.live = false;
+        VX_HIP(hipEventSynchronize(c->slots[si].done));
+        const uint8_t* out = c->merkle[si].h + (size_t)c->merkle_rows * 48;
+        if (roots_out) std::memcpy(roots_out + r.first * 32, out, (size_t)r.m * 32);
+        std::memcpy(matched_out + r.first, out + (size_t)r.m * 32, r.m);
+        for (uint32_t k = 0; k < r.m; ++k) n_bad += matched_out[r.first + k] == 0;
+        return 0;
+    };
+    size_t next = 0;
+    for (size_t k = 0; next < n && !rc; ++k) {
+        const size_t si = k % nslots;
+        Slot& s = c->slots[si];
+        rc = harvest_round(si);  // the slot's last round: its stage and buffers are free again
+        if (rc) break;
+        const uint64_t R = c->merkle_rows;
+        uint8_t* h_in = c->merkle[si].h;
+        uint8_t* d_in = c->merkle[si].d;
+        uint8_t* d_out = d_in + R * 48;
+        uint8_t* d_leaves = d_in + R * 96;
+        // the pieces of this round: as many as the arena and the leaf rows hold
+        uint32_t m = 0;
+        uint64_t bytes = 0;
+        while (next + m < n && m < max_pieces && bytes + align_up(lens[next + m], kAlign) <= s.arena_cap)
+            bytes += align_up(lens[next + m++], kAlign);
+        if (m == 0) {
+            rc = fail(VX_ERANGE, "vx_merkle_verify_batch: a piece does not fit a slot");
+            break;
+        }
+        uint64_t* offs = reinterpret_cast<uint64_t*>(h_in + (size_t)m * 32);
+        uint32_t* hl = reinterpret_cast<uint32_t*>(h_in + (size_t)m * 40);
+        uint8_t* hw = h_in + (size_t)m * 44;
+        std::memcpy(h_in, expected + next * 32, (size_t)m * 32);
+        // Plain memory goes through the pinned stage, consecutive pieces in one
+        // copy; a registered piece is pinned already and is copied from where it lies.
+        uint64_t at = 0, run_lo = 0;
+        bool in_run = false;
+        auto flush_run = [&](uint64_t hi) -> int {
+            if (in_run && hi > run_lo)
+                VX_HIP(hipMemcpyAsync(s.d_arena + run_lo, s.h_stage + run_lo, hi - run_lo, hipMemcpyHostToDevice,
+                                      s.stream));
+            in_run = false;
+            return 0;
+        };
+        for (uint32_t j = 0; j < m && !rc; ++j) {
+            const size_t i = next + j;
+            offs[j] = at;
+            hl[j] = lens[i];
+            hw[j] = log2w ? log2w[i] : (uint8_t)log2_width;
+            if (lens[i] && is_registered(c, ptrs[i], lens[i])) {
+                rc = flush_run(at);
+                if (!rc && hipMemcpyAsync(s.d_arena + at, ptrs[i], lens[i], hipMemcpyHostToDevice, s.stream) !=
+                               hipSuccess)
+                    rc = fail(VX_EDEVICE, "vx_merkle_verify_batch: copy from registered memory failed");
+            } else if (lens[i]) {
+                rc = ensure_stage(c, s);
+                if (rc) break;
+                if (!in_run) {
+                    in_run = true;
+                    run_lo = at;
+                }
+                std::memcpy(s.h_stage + at, ptrs[i], lens[i]);
+                c->stats.staged_bytes += lens[i];
+            }
+            at += align_up(lens[i], kAlign);
+            n_bytes += lens[i];
+        }
+        if (!rc) rc = flush_run(at);
+        if (rc) break;
+        hipError_t e = hipMemcpyAsync(d_in, h_in, (size_t)m * 45, hipMemcpyHostToDevice, s.stream);
+        if (e == hipSuccess)
+            e = vx::launch_merkle_ragged(s.d_arena, reinterpret_cast<const uint64_t*>(d_in + (size_t)m * 32),
+                                                reinterpret_cast<const uint32_t*>(d_in + (size_t)m * 40),
+                                                d_in + (size_t)m * 44, m, log2_width, d_leaves, d_out, d_in,
+                                                d_out + (size_t)m * 32, s.stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_in + R * 48, d_out, (size_t)m * 33, hipMemcpyDeviceToHost, s.stream);
+        if (e == hipSuccess) e = hipEventRecord(s.done, s.stream);
+        if (e != hipSuccess) {
+            rc = hip_fail(e, "vx_merkle_verify_batch: enqueue");
+            break;
+        }
+        rounds[si] = Round{next, m, true};
+        next += m;
+        ++n_rounds;
+    }
+    // Take what is left in launch order; after an error only wait, so no copy
+    // still reads a stage or the caller's registered memory when this returns.
+    for (size_t si = 0; si < nslots; ++si) {
+        if (!rc) {
+            rc = harvest_round(si);
+        } else if (c->slots[si].stream) {
+            (void)hipStreamSynchronize(c->slots[si].stream);
+        }
+    }
+    if (rc) return rc;
+    c->stats.pieces_completed += n;
+    c->stats.pieces_mismatched += n_bad;
+    c->stats.bytes_completed += n_bytes;
+    c->stats.batches += n_rounds;
+    return 0;
+}
+
+int vx_merkle_device_blocks(const void* d_stage, const uint32_t* d_rows, const uint32_t* d_lens, uint32_t n_blocks,
+                            void* d_leaves, void* stream) {
+    if (n_blocks == 0) return 0;
+    if (!d_stage || !d_rows || !d_lens || !d_leaves) return fail(VX_EINVAL, "vx_merkle_device_blocks: NULL argument");
+    if ((reinterpret_cast<uintptr_t>(d_stage) | reinterpret_cast<uintptr_t>(d_leaves)) & 15)
+        return fail(VX_EINVAL, "vx_merkle_device_blocks: d_stage and d_leaves must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_rows) | reinterpret_cast<uintptr_t>(d_lens)) & 3)
+        return fail(VX_EINVAL, "vx_merkle_device_blocks: d_rows and d_lens must be 4-byte aligned");
+    hipError_t e = vx::launch_merkle_blocks(static_cast<const uint8_t*>(d_stage), d_rows, d_lens, n_blocks,
+                                            static_cast<uint8_t*>(d_leaves), static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "merkle block kernel launch");
+    return 0;
+}
+
+int vx_merkle_device_nodes(const void* d_leaves, const uint8_t* d_log2w, uint32_t n, uint32_t log2_width,
+                           void* d_roots, const void* d_expected, void* d_matched, void* stream) {
+    if (n == 0) return 0;
+    int rc = merkle_args("vx_merkle_device_nodes", d_leaves, d_leaves, n, log2_width);
+    if (rc) return rc;
+    if ((reinterpret_cast<uintptr_t>(d_roots) & 15) || (reinterpret_cast<uintptr_t>(d_expected) & 3))
+        return fail(VX_EINVAL, "vx_merkle_device_nodes: d_roots must be 16-byte and d_expected 4-byte aligned");
+    const bool verdict = d_expected && d_matched;
+    hipError_t e = vx::launch_merkle_nodes(static_cast<const uint8_t*>(d_leaves), d_log2w, n, log2_width,
+                                           static_cast<uint8_t*>(d_roots),
+                                           verdict ? static_cast<const uint8_t*>(d_expected) : nullptr,
+                                           verdict ? static_cast<uint8_t*>(d_matched) : nullptr,
+                                           static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "merkle node kernel launch");
+    return 0;
+}
+
+// ---- vx_merkle_verify_files: the v2 re-verify from disk ----
+// Rounds of 16 KiB blocks packed by vx_merkle::Rounds, one slot's pinned stage
+// each.  Per round, on the slot's stream: the data H2D, the rows | lens table
+// in one H2D, the block kernel, and the node kernels of the groups of pieces
+// the round finished, with verdicts into the call's device rows; the kernels
+// wait for the previous round's (one event), the copies do not.  Reads run up
+// to kReadahead rounds ahead of the round being enqueued.
+
+constexpr uint64_t kMerkleRoundCap = 64ull << 20;  // a round's stage bytes at most
+constexpr uint32_t kMerkleRunBlocks = 128;         // one pread: 2 MiB at most (32 reads for 16 readers per full round)
+
+static int ensure_merkle_files(vx_ctx* c, uint64_t window_rows, uint64_t entries, uint64_t count) {
+    vx_ctx::MerkleFiles& m = c->mfiles;
+    const char* oom = "vx_merkle_verify_files: buffer allocation failed";
+    if (!m.chain && hipEventCreateWithFlags(&m.chain, hipEventDisableTiming) != hipSuccess)
+        return fail(VX_EDEVICE, "vx_merkle_verify_files: event creation failed");
+    if (m.window_rows < window_rows) {
+        if (m.d_window) (void)hipFree(m.d_window);
+        m.d_window = nullptr;
+        m.window_rows = 0;
+        if (hipMalloc(&m.d_window, window_rows * 32) != hipSuccess) return fail(VX_ENOMEM, oom);
+        m.window_rows = window_rows;
+    }
+    if (m.tab_entries < entries || m.h_tab.size() != c->slots.size()) {
+        for (uint32_t* p : m.h_tab)
+            if (p) (void)hipHostFree(p);
+        for (uint32_t* p : m.d_tab)
+            if (p) (void)hipFree(p);
+        m.h_tab.assign(c->slots.size(), nullptr);
+        m.d_tab.assign(c->slots.size(), nullptr);
+        m.tab_entries = 0;
+        for (size_t k = 0; k < c->slots.size(); ++k)
+            if (hipHostMalloc(&m.h_tab[k], entries * 8, hipHostMallocDefault) != hipSuccess ||
+                hipMalloc(&m.d_tab[k], entries * 8) != hipSuccess)
+                return fail(VX_ENOMEM, oom);
+        m.tab_entries = entries;
+    }
+    if (m.call_cap < count) {
+        if (m.d_call) (void)hipFree(m.d_call);
+        m.d_call = nullptr;
+        m.call_cap = 0;
+        const uint64_t cap = std::max<uint64_t>(count, 4096);
+        if (hipMalloc(&m.d_call, cap * 34) != hipSuccess) return fail(VX_ENOMEM, oom);
+        m.call_cap = cap;
+    }
+    return 0;
+}
+
+static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                                 uint32_t piece_length, const uint8_t* expected, size_t n_pieces, size_t first,
+                                 size_t count, uint8_t* matched_out, uint32_t io_threads) {
+    const char* who = "vx_merkle_verify_files";
+    if (!c) return fail(VX_EINVAL, std::string(who) + ": NULL context");
+    if ((nfiles && (!paths || !file_lengths)) || (n_pieces && !expected) || (count && !matched_out))
+        return fail(VX_EINVAL, std::string(who) + ": NULL paths/file_lengths/expected/matched_out");
+    if (piece_length < VX_MERKLE_BLOCK || (piece_length & (piece_length - 1)))
+        return fail(VX_EINVAL, std::string(who) + ": piece_length must be a power of two >= 16384");
+    if (n_pieces != vx_merkle::torrent_pieces(file_lengths, nfiles, piece_length))
+        return fail(VX_EINVAL, std::string(who) + ": n_pieces does not match the files");
+    if (first > n_pieces || count > n_pieces - first)
+        return fail(VX_EINVAL, std::string(who) + ": piece range outside the torrent");
+    int rc = begin_bulk_call(c, who, /*need_idle=*/true);
+    if (rc) return rc;
+    if (count == 0) return 0;
+    const uint64_t bpr64 = std::min<uint64_t>(c->slots[0].arena_cap, kMerkleRoundCap) / VX_MERKLE_BLOCK;
+    if (bpr64 == 0) return fail(VX_ERANGE, std::string(who) + ": a slot holds no 16 KiB block");
+    const uint32_t bpr = (uint32_t)bpr64;
+    rc = set_device(c);
+    if (rc) return rc;
+    const uint32_t R =vx_merkle::Rounds::window_for(bpr, piece_length);
+    const uint32_t entries = 2 * bpr + piece_length / VX_MERKLE_BLOCK;
+    if ((rc = ensure_merkle_files(c, R, entries, count))) return rc;
+    vx_ctx::MerkleFiles& mf = c->mfiles;
+    uint8_t* d_exp = mf.d_call;
+    uint8_t* d_match = mf.d_call + mf.call_cap * 32;
+    uint8_t* d_lw = mf.d_call + mf.call_cap * 33;
+
+    const uint64_t t_call = vx_files::Readers::now_ns();
+    c->last_verify = vx_verify_trace{};
+    c->last_rounds.clear();
+    c->verify_t0_ns = t_call;
+    {
+        std::vector<uint8_t> lw(count);
+        vx_merkle::PieceCursor pc(file_lengths, nfiles, piece_length);
+        pc.seek(first);
+        for (size_t i = 0; i < count; ++i, pc.next()) lw[i] = (uint8_t)pc.log2w();
+        if (hipMemcpy(d_exp, expected + 32 * first, count * 32, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_lw, lw.data(), count, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemset(d_match, 0, count) != hipSuccess ||
+            hipStreamSynchronize(nullptr) != hipSuccess)  // (the slot streams do not wait for the null stream)
+            return fail(VX_EDEVICE, std::string(who) + ": expected-table upload failed");
+    }
+    std::vector<int> fds(nfiles, -1);
+    for (size_t f = 0; f < nfiles; ++f) fds[f] = open(paths[f], O_RDONLY | O_CLOEXEC);
+    const int nthreads = io_threads ? (int)io_threads : (int)std::max(1u, std::min(16u, usable_cpus()));
+    std::vector<uint8_t> bad(count, 0);
+    std::memset(matched_out, 0, count);
+    const size_t nslots = c->slots.size();
+    // Reads run ahead as far as the slots allow: a v2 round carries no state,
+    // so a slot is free again as soon as its own round's kernels are done, and
+    // only the round about to be enqueued ever waits for one.
+    const size_t depth = nslots - 1;
+    uint64_t n_rounds = 0, n_bytes = 0, copy_bytes = 0;
+    using clk = std::chrono::steady_clock;
+    auto t_last_enqueue = clk::now();
+    {
+        const std::vector<vx_files::FileSpan> no_spans;
+        const vx_files::DirectIo dio(fds, c->cfg.direct_io != 0);
+        vx_files::Readers rd(nthreads, no_spans, fds, piece_length, bad.data(), first, &dio, true);
+        vx_merkle::Rounds pack(file_lengths, nfiles, piece_length, first, count, bpr, R, entries, kMerkleRunBlocks);
+        std::vector<vx_merkle::Round> round(nslots);
+        std::vector<std::vector<vx_files::ReadItem>> items(nslots);
+        std::vector<uint64_t> ticket(nslots, 0);
+        std::vector<uint8_t> live(nslots, 0);  // the slot carries an enqueued round
+        bool more = true, have_prev = false;
+        size_t nr = 0;  // next round to read
+        for (size_t ne = 0; !rc; ++ne) {
+            while (more && nr <= ne + depth && !rc) {
+                const size_t si = nr % nslots;
+                Slot& s = c->slots[si];
+                if (live[si]) {  // the round this slot carried: its stage and tables are free again after it
+                    const hipError_t q = nr == ne ? hipEventSynchronize(s.done) : hipEventQuery(s.done);
+                    if (q == hipErrorNotReady) break;  // read-ahead takes only a slot that is free now
+                    if (q != hipSuccess) {
+                        rc = fail(VX_EDEVICE, std::string(who) + ": wait failed");
+                        break;
+                    }
+                    live[si] = 0;
+                }
+                if (!(more = pack.next(round[si]))) break;
+                if ((rc = ensure_stage(c, s))) break;
+                auto& it = items[si];
+                it.clear();
+                for (const vx_merkle::Read& r : round[si].reads) {
+                    vx_files::ReadItem x{s.h_stage + (uint64_t)r.stage_block * VX_MERKLE_BLOCK, r.piece, 0, r.len};
+                    x.file = (int32_t)r.file;
+                    x.file_off = (int64_t)r.file_off;
+                    it.push_back(x);
+                }
+                ticket[si] = rd.submit(it);
+                ++nr;
+            }
+            if (rc || ne == nr) break;
+            const size_t si = ne % nslots;
+            Slot& s = c->slots[si];
+            const vx_merkle::Round& r = round[si];
+            rd.wait(ticket[si]);
+            const uint32_t m = (uint32_t)r.rows.size();
+            uint32_t* h_tab = mf.h_tab[si];
+            uint32_t* d_tab = mf.d_tab[si];
+            std::memcpy(h_tab, r.rows.data(), (size_t)m * 4);
+            std::memcpy(h_tab + m, r.lens.data(), (size_t)m * 4);
+            hipError_t e = hipMemcpyAsync(s.d_arena, s.h_stage, r.bytes, hipMemcpyHostToDevice, s.stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_tab, h_tab, (size_t)m * 8, hipMemcpyHostToDevice, s.stream);
+            if (e == hipSuccess && have_prev) e = hipStreamWaitEvent(s.stream, mf.chain, 0);
+#ifdef VX_TEST_HOOKS
+            if (e == hipSuccess && c->fail_launch_after >= 0 && c->fail_launch_after-- == 0) {
+                rc = fail(VX_EDEVICE, std::string(who) + ": injected launch failure (vx_tuning_fail_launch_after)");
+                break;
+            }
+#endif
+            if (e == hipSuccess) e = vx::launch_merkle_blocks(s.d_arena, d_tab, d_tab + m, m, mf.d_window, s.stream);
+            for (const vx_merkle::Nodes& g : r.nodes) {
+                if (e != hipSuccess) break;
+                const uint64_t k = g.first - first;
+                e = vx::launch_merkle_nodes(mf.d_window + (size_t)g.row0 * 32, d_lw + k, g.n, g.log2_width, nullptr,
+                                            d_exp + k * 32, d_match + k, s.stream);
+            }
+            if (e == hipSuccess) e = hipEventRecord(mf.chain, s.stream);
+            if (e == hipSuccess) e = hipEventRecord(s.done, s.stream);
+            if (e != hipSuccess) {
+                rc = hip_fail(e, "vx_merkle_verify_files: enqueue");
+                break;
+            }
+            have_prev = true;
+            live[si] = 1;
+            ++n_rounds;
+            n_bytes += r.file_bytes;
+            copy_bytes += r.bytes;
+            t_last_enqueue = clk::now();
+        }
+        rd.wait();  // error path: no read may still target a stage
+        for (size_t si = 0; si < nslots; ++si)  // ... and no copy may still read one
+            if (c->slots[si].stream && hipStreamSynchronize(c->slots[si].stream) != hipSuccess && !rc)
+                rc = fail(VX_EDEVICE, std::string(who) + ": a round failed on the device");
+        std::vector<uint8_t> verdict(count);
+        if (!rc && hipMemcpy(verdict.data(), d_match, count, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(VX_EDEVICE, std::string(who) + ": verdict download failed");
+        vx_verify_trace& vt = c->last_verify;
+        vt.tail_ms = std::chrono::duration<double, std::milli>(clk::now() - t_last_enqueue).count();
+        trace_reads(vt, rd, dio, t_call);
+        vt.rounds = (uint32_t)n_rounds;
+        vt.copy_bytes = copy_bytes;
+        vt.chunk_bytes = (uint64_t)bpr * VX_MERKLE_BLOCK;
+        if (!rc) {
+            uint64_t mism = 0;
+            for (size_t i = 0; i < count; ++i) {
+                matched_out[i] = verdict[i] && !bad[i] ? 1 : 0;
+                mism += !verdict[i] && !bad[i];  // I/O errors count in io_errors only
+            }
+            c->stats.pieces_completed += count;
+            c->stats.pieces_mismatched += mism;
+            c->stats.bytes_completed += n_bytes;
+            c->stats.batches += n_rounds;
+        }
+    }
+    return end_files_call(c, fds, bad, t_call, rc);
+}
+
+int64_t vx_merkle_verify_files_range(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                                     uint32_t piece_length, const uint8_t* expected, size_t n_pieces, size_t first,
+                                     size_t count, uint8_t* matched_out, uint32_t io_threads) {
+    return merkle_files_impl(c, paths, file_lengths, nfiles, piece_length, expected, n_pieces, first, count,
+                             matched_out, io_threads);
+}
+
+int64_t vx_merkle_verify_files(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                               uint32_t piece_length, const uint8_t* expected, size_t n_pieces, uint8_t* matched_out,
+                               uint32_t io_threads) {
+    return merkle_files_impl(c, paths, file_lengths, nfiles, piece_length, expected, n_pieces, 0, n_pieces,
+                             matched_out, io_threads);
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // vx_merkle_rounds.hpp — host-only round packer of the BitTorrent v2 re-verify
-// from disk (vx_merkle_verify_files in vx_engine.hip).  No HIP in here: the
+// from disk (vx_merkle_verify_files in vx_merkle.hip).  No HIP in here: the
 // packer is tested on the CPU (tests/native/merkle_rounds_dump.cpp).
 //
 // A v2 piece's 16 KiB blocks are independent, so a round is any run of blocks:
