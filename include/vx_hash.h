@@ -528,6 +528,21 @@ int vx_merkle_device_uniform(const void* d_base, uint64_t stride, uint32_t len, 
 int vx_merkle_device_ragged(const void* d_base, const uint64_t* d_offsets, const uint32_t* d_lens,
                             const uint8_t* d_log2w, uint32_t n, uint32_t log2_width, void* d_leaves, void* d_roots,
                             const void* d_expected, void* d_matched, void* stream);
+/* The same batch through the fused piece kernel, which keeps no leaf layer:
+ * roots and verdicts only, the leaf rows live in LDS and never reach HBM (the
+ * async path's kernel, vx_merkle_submit).  Arguments and checks as for
+ * vx_merkle_device_ragged, with d_work in place of d_leaves:
+ *   log2_width <= 8   one launch; d_work is unused and may be NULL.
+ *   log2_width  > 8   d_work (16-byte aligned) holds T = n << (log2_width - 8)
+ *                     rows of 32 bytes, the tops of the pieces' 256-leaf tiles
+ *                     (piece i's at row i << (log2_width - 8)), followed by n
+ *                     bytes, max(d_log2w[i] - 8, 0) per piece: T * 32 + n bytes
+ *                     in all, written by the first launch and reduced by a
+ *                     second (the node kernel at width log2_width - 8).
+ * Enqueue-only; n == 0 launches nothing. */
+int vx_merkle_device_pieces(const void* d_base, const uint64_t* d_offsets, const uint32_t* d_lens,
+                            const uint8_t* d_log2w, uint32_t n, uint32_t log2_width, void* d_work, void* d_roots,
+                            const void* d_expected, void* d_matched, void* stream);
 /* Root of a layer of n hashes (32 bytes each) that stand `height` levels above
  * the leaves: the layer is padded to the next power of two with pad(height),
  * each level above with the next pad hash (how a client checks a received
@@ -551,6 +566,34 @@ int vx_merkle_pad_hash(uint32_t height, uint8_t* out);
 int vx_merkle_verify_batch(vx_ctx* ctx, const uint8_t* const* ptrs, const uint32_t* lens, const uint8_t* log2w,
                            size_t n, uint32_t piece_length, const uint8_t* expected, uint8_t* matched_out,
                            uint8_t* roots_out);
+
+/* The v2 download path: vx_submit / vx_poll for a BEP 52 piece.  One
+ * completion; `root` is the piece's merkle root, `matched` = (root ==
+ * expected) or 0 when the piece was submitted without one. */
+typedef struct vx_merkle_completion {
+    uint64_t tag;
+    uint8_t matched;
+    uint8_t root[VX_SHA256_LEN];
+    uint8_t _pad[7];
+} vx_merkle_completion; /* 48 bytes */
+/* Queue data[0..len) as a v2 piece whose tree has 2^log2w leaf slots and
+ * compare its root with expected[0..32) (NULL: the root is returned, matched
+ * = 0).  len <= VX_MERKLE_BLOCK << log2w, and VX_MERKLE_BLOCK << log2w is at
+ * most max_piece_len rounded up to a power of two (VX_EINVAL otherwise; len >
+ * max_piece_len is VX_ERANGE).  Everything else is vx_submit's: the ownership
+ * rule (the piece is taken iff the call returns 0), the return codes, VX_EBUSY
+ * under refuse_when_full, the placement of registered and plain pieces.  v1
+ * and v2 pieces share the context's batch slots, pending count, vx_flush,
+ * vx_drain and statistics; a slot holds one kind, so a change of kind launches
+ * the open batch.  A v2 slot is always copied or gathered into HBM first
+ * (never hashed zero-copy) and hashed by the fused piece kernel: one launch
+ * for trees of at most 256 leaves, two above. */
+int vx_merkle_submit(vx_ctx* ctx, uint64_t tag, const uint8_t* data, uint32_t len, uint32_t log2w,
+                     const uint8_t* expected);
+/* vx_poll for v2 pieces: vx_poll hands out v1 completions only, this call v2
+ * only.  After a device failure each returns the results it still holds, then
+ * the error. */
+int64_t vx_merkle_poll(vx_ctx* ctx, vx_merkle_completion* out, size_t max);
 
 /* The two halves of the device entries on their own, for a caller that
  * streams blocks in rounds of its own (the re-verify below does).

@@ -18,6 +18,15 @@
 #define VX_TUNING_H
 #include <stddef.h>
 #include <stdint.h>
+/* Compile-time A/B of the v2 async path's kernel (vx_merkle_submit, DESIGN.md
+ * §3.7): 1 (the default) hashes a v2 slot with the fused piece kernel, leaves
+ * reduced in LDS; 0 with the leaf + node kernels of vx_merkle_device_ragged
+ * and a leaf array per slot.  Build the engine with -DVX_MERKLE_ASYNC_FUSED=0
+ * for the other leg. */
+#ifndef VX_MERKLE_ASYNC_FUSED
+#define VX_MERKLE_ASYNC_FUSED 1
+#endif
+
 #ifdef __cplusplus
 extern "C" {
 #endif

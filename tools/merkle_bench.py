@@ -25,8 +25,14 @@ one chain); the ratio is recorded and the tool exits 1 below it.
 buffer beside merkle_uniform, K timed runs of each, alternating; both are
 recorded with the spread between merkle_uniform's own runs.
 
+--pieces-leg K: on 65,536 x 256 KiB and 1,024 x 4 MiB the fused piece kernel
+(merkle_pieces, the async path's kernel) runs beside the leaf + node pair
+(merkle_ragged) on the same buffer, K alternating timed runs of each, recorded
+with the spread between the pair's own runs.
+
   python tools/merkle_bench.py --out profiles/merkle/device.json [--isa sha256_kernels.s]
   python tools/merkle_bench.py --shapes 0 --blocks-leg 3 --out profiles/merkle/blocks.json
+  python tools/merkle_bench.py --shapes 0,1 --pieces-leg 3 --no-sha1 --out profiles/merkle/pieces.json
 """
 from __future__ import annotations
 
@@ -130,6 +136,10 @@ def main() -> int:
     ap.add_argument("--blocks-leg", type=int, default=0, metavar="K",
                     help="on 65,536 x 256 KiB also run merkle_blocks + merkle_nodes beside merkle_uniform, "
                          "K alternating timed runs of each")
+    ap.add_argument("--pieces-leg", type=int, default=0, metavar="K",
+                    help="on 65,536 x 256 KiB and 1,024 x 4 MiB also run merkle_pieces (the fused kernel) beside "
+                         "merkle_ragged (leaf + node), K alternating timed runs of each")
+    ap.add_argument("--no-sha1", action="store_true", help="skip the SHA-1 kernel beside each shape (and the 2x condition)")
     args = ap.parse_args()
 
     isa = isa_valu_per_block(args.isa) if args.isa else None
@@ -214,7 +224,41 @@ def main() -> int:
                     sorted(rates["merkle_uniform"])[len(rates["merkle_uniform"]) // 2], 1)}
             del b_rows, b_lens, b_leaves, b_roots
 
-        if sha1_kind:
+        if idx in (0, 1) and args.pieces_leg:
+            # The fused piece kernel (merkle_pieces: leaves reduced in LDS, no
+            # leaf array) against the leaf + node pair (merkle_ragged) on the
+            # same buffer, alternating; the spread between the pair's own runs
+            # is the margin.
+            p_offs = torch.arange(n, dtype=torch.int64, device=dev) * plen
+            p_lens = torch.full((n,), plen, dtype=torch.int32, device=dev)
+            r_roots = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+            p_roots = torch.full((n, 32), 0xFF, dtype=torch.uint8, device=dev)
+            vdev.merkle_ragged(data, p_offs, p_lens, log2_width, leaves=leaves, roots=r_roots)  # validates once
+
+            def pair():
+                vdev.merkle_ragged(data, p_offs, p_lens, log2_width, leaves=leaves, roots=r_roots, validate=False)
+
+            def fused():
+                vdev.merkle_pieces(data, p_offs, p_lens, log2_width, roots=p_roots, validate=False)
+
+            fused()
+            torch.cuda.synchronize(dev)
+            if not (torch.equal(p_roots, roots) and torch.equal(r_roots, roots)):
+                raise SystemExit(f"{n} x {plen}: merkle_pieces differs from the leaf + node pair")
+            runs = {"merkle_ragged": [], "merkle_pieces": []}
+            for _ in range(args.pieces_leg):
+                for name, fn in (("merkle_ragged", pair), ("merkle_pieces", fused)):
+                    t, clock = timed(fn, args.warmup, steps, dev)
+                    runs[name].append(record(t, clock, nbytes, n << log2_width, BLOCK // 64, valu256, simds))
+            rates = {k: [r["GiB_per_s"] for r in v] for k, v in runs.items()}
+            med = {k: sorted(v)[len(v) // 2] for k, v in rates.items()}
+            shape["pieces_leg"] = {
+                "runs": runs, "GiB_per_s": rates, "GiB_per_s_median": med,
+                "merkle_ragged_spread": round(max(rates["merkle_ragged"]) - min(rates["merkle_ragged"]), 1),
+                "pieces_minus_ragged_median": round(med["merkle_pieces"] - med["merkle_ragged"], 1)}
+            del p_offs, p_lens, r_roots, p_roots
+
+        if sha1_kind and not args.no_sha1:
             digests = torch.empty((n, 20), dtype=torch.uint8, device=dev)
             if sha1_kind == "sha1_uniform":
                 def sha1():

@@ -53,6 +53,7 @@ EXPORTS = (
     "vx_merkle_device_uniform", "vx_merkle_device_ragged", "vx_merkle_device_root", "vx_merkle_pad_hash",
     "vx_merkle_verify_batch",
     "vx_merkle_device_blocks", "vx_merkle_device_nodes", "vx_merkle_verify_files", "vx_merkle_verify_files_range",
+    "vx_merkle_device_pieces", "vx_merkle_submit", "vx_merkle_poll",
 )
 # ... plus include/vx_tuning.h and include/vx_synth.h: libvortex_amd_tuning.so only.
 TUNING_EXPORTS = (
@@ -76,6 +77,12 @@ class VxError(RuntimeError):
 class vx_completion(ctypes.Structure):
     _fields_ = [("tag", ctypes.c_uint64), ("matched", ctypes.c_uint8), ("digest", ctypes.c_uint8 * 20),
                 ("_pad", ctypes.c_uint8 * 3)]
+
+
+class vx_merkle_completion(ctypes.Structure):
+    """A v2 piece's completion (vx_merkle_poll): 48 bytes."""
+    _fields_ = [("tag", ctypes.c_uint64), ("matched", ctypes.c_uint8), ("root", ctypes.c_uint8 * 32),
+                ("_pad", ctypes.c_uint8 * 7)]
 
 
 ABI_VERSION = 3
@@ -199,6 +206,9 @@ def _declare(L: ctypes.CDLL, tuning: bool = False) -> None:
         "vx_merkle_verify_files": ([vp, vp, vp, c.c_size_t, c.c_uint32, vp, c.c_size_t, vp, c.c_uint32], c.c_int64),
         "vx_merkle_verify_files_range": ([vp, vp, vp, c.c_size_t, c.c_uint32, vp, c.c_size_t, c.c_size_t,
                                           c.c_size_t, vp, c.c_uint32], c.c_int64),
+        "vx_merkle_device_pieces": ([vp, vp, vp, vp, c.c_uint32, c.c_uint32, vp, vp, vp, vp, vp], c.c_int),
+        "vx_merkle_submit": ([vp, c.c_uint64, vp, c.c_uint32, c.c_uint32, vp], c.c_int),
+        "vx_merkle_poll": ([vp, c.POINTER(vx_merkle_completion), c.c_size_t], c.c_int64),
     }
     if tuning:
         sig.update({

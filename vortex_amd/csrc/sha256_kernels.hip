@@ -20,6 +20,11 @@
 //    piece tile by tile and then the tiles' tops.  Under 1 % of the leaf work.
 //  * layer kernel (vx_merkle_device_root): the same tile reduction over a
 //    layer of n hashes, missing rows filled with the pad hash of the level.
+//  * piece kernel (vx_merkle_device_pieces, the async path of
+//    vx_merkle_submit): the leaf kernel's lanes with the tree fused on.  A
+//    workgroup's 256 leaf rows stay in LDS and are reduced there; trees of at
+//    most 256 leaves finish in the one launch, wider ones leave a top per
+//    256-leaf tile for the node kernel.  No leaf layer is kept.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -213,7 +218,8 @@ struct Rows {
 
 // One level in place: the first 2*count rows become count rows.  Every thread
 // of the workgroup calls this (barriers inside).
-__device__ __forceinline__ void reduce_level(Rows& t, uint32_t count) {
+template <class Tile>
+__device__ __forceinline__ void reduce_level(Tile& t, uint32_t count) {
     const uint32_t i = threadIdx.x;
     uint4 o0, o1;
     if (i < count) node_hash(o0, o1, t.lo[2 * i], t.hi[2 * i], t.lo[2 * i + 1], t.hi[2 * i + 1]);
@@ -241,6 +247,98 @@ __device__ __forceinline__ void emit_root(const Row& r, uint32_t piece, uint8_t*
         const bool ok = (x[0] == r.lo.x) & (x[1] == r.lo.y) & (x[2] == r.lo.z) & (x[3] == r.lo.w) &
                         (x[4] == r.hi.x) & (x[5] == r.hi.y) & (x[6] == r.hi.z) & (x[7] == r.hi.w);
         matched[piece] = ok ? 1 : 0;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Fused piece kernel (the async download path): the leaf
+// kernel's lanes, but a workgroup keeps its 256 leaf rows in LDS and reduces
+// them there, so no leaf row reaches HBM and a batch of trees of at most 256
+// leaves is one launch.
+//  * log2_width <= kPieceTileLog2: a workgroup holds 256 >> log2_width whole
+//    pieces; after level L every piece with log2w == L emits its root.
+//  * wider: a workgroup is one 256-leaf tile of one piece and stores the
+//    tile's top (row 0 after min(log2w, 8) levels) to tops[(piece <<
+//    (log2_width - 8)) + tile], for the tiles under the piece's own root only;
+//    tile 0 also stores log2w_top[piece] = max(log2w - 8, 0).  The host then
+//    runs the node kernel over tops at width log2_width - 8: the kernel
+//    boundary is what orders the tops between workgroups.
+constexpr int kPieceTileLog2 = 8;
+static_assert((1 << kPieceTileLog2) == kBlock, "one leaf per thread of the workgroup");
+
+struct PieceRows {
+    uint4 lo[kBlock];
+    uint4 hi[kBlock];
+};
+
+__global__ __launch_bounds__(kBlock) void merkle_piece_kernel(const uint8_t* __restrict__ base,
+                                                              const uint64_t* __restrict__ offsets,
+                                                              const uint32_t* __restrict__ lens,
+                                                              const uint8_t* __restrict__ log2w, uint32_t n,
+                                                              uint32_t log2_width, uint8_t* __restrict__ tops,
+                                                              uint8_t* __restrict__ log2w_top,
+                                                              uint8_t* __restrict__ roots,
+                                                              const uint8_t* __restrict__ expected,
+                                                              uint8_t* __restrict__ matched) {
+    __shared__ PieceRows t;
+    const uint32_t i = threadIdx.x;
+    {
+        // the leaf phase, as merkle_leaf_kernel<true>
+        const uint32_t g = blockIdx.x * kBlock + i;
+        const uint32_t rows = n << log2_width;
+        // Lanes past the last row redo row rows-1 (in bounds, the wave stays
+        // convergent); their LDS rows belong to pieces >= n and are never emitted.
+        const uint32_t gg = g < rows ? g : rows - 1;
+        const uint32_t piece = gg >> log2_width;
+        const uint32_t slot = gg & ((1u << log2_width) - 1);
+        const uint32_t plen = lens[piece];
+        const uint8_t* p = base + offsets[piece];
+        const uint64_t start = (uint64_t)slot * kLeaf;
+        const uint32_t leaf_len = start < plen ? (plen - start < kLeaf ? (uint32_t)(plen - start) : kLeaf) : 0;
+        const uint32_t ng = leaf_len >> 7;
+        const uint32_t ng_wave = __builtin_amdgcn_readfirstlane(wave_max(ng));
+        p += start < plen ? start : 0;
+        State s = sha256::iv();
+        stream_groups(s, reinterpret_cast<const uint4*>(p), ng, ng_wave);
+        if (leaf_len == kLeaf) {
+            sha256::compress_const(s, kPadLeaf);
+        } else if (leaf_len) {
+            finish_tail(s, p + (size_t)ng * 128, leaf_len & 127u, leaf_len);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s.h[k] = 0;  // beyond the piece: the zero hash, not a hash of anything
+        }
+        t.lo[i] = make_uint4(sha256::bswap(s.h[0]), sha256::bswap(s.h[1]), sha256::bswap(s.h[2]), sha256::bswap(s.h[3]));
+        t.hi[i] = make_uint4(sha256::bswap(s.h[4]), sha256::bswap(s.h[5]), sha256::bswap(s.h[6]), sha256::bswap(s.h[7]));
+    }
+    __syncthreads();
+    if (log2_width <= (uint32_t)kPieceTileLog2) {
+        const uint32_t per = (uint32_t)kBlock >> log2_width;  // pieces of this workgroup: one thread each
+        const uint32_t piece = blockIdx.x * per + i;
+        const bool mine = i < per && piece < n;
+        const uint32_t want = mine ? (log2w ? log2w[piece] : log2_width) : 0xFFFFFFFFu;
+        for (uint32_t L = 0;; ++L) {
+            if (want == L)
+                emit_root(Row{t.lo[(i << log2_width) >> L], t.hi[(i << log2_width) >> L]}, piece, roots, expected,
+                          matched);
+            if (L == log2_width) break;
+            reduce_level(t, (uint32_t)kBlock >> (L + 1));
+        }
+    } else {
+        const uint32_t tshift = log2_width - kPieceTileLog2;
+        const uint32_t piece = blockIdx.x >> tshift;  // (< n: n << log2_width rows are whole tiles)
+        const uint32_t tile = blockIdx.x & ((1u << tshift) - 1);
+        const uint32_t want = log2w ? log2w[piece] : log2_width;  // (workgroup-uniform)
+        const uint32_t levels = want < (uint32_t)kPieceTileLog2 ? want : (uint32_t)kPieceTileLog2;
+        // (a log2w above log2_width is not a level of this tree: clamped, it stays in bounds and emits nothing)
+        const uint32_t want_top = want - levels < tshift + 1 ? want - levels : tshift + 1;
+        for (uint32_t L = 0; L < levels; ++L) reduce_level(t, (uint32_t)kBlock >> (L + 1));
+        if (i == 0 && tile < (1u << want_top)) {
+            uint4* o = reinterpret_cast<uint4*>(tops + ((size_t)(piece << tshift) + tile) * 32);
+            o[0] = t.lo[0];
+            o[1] = t.hi[0];
+            if (tile == 0) log2w_top[piece] = (uint8_t)want_top;
+        }
     }
 }
 
@@ -393,6 +491,22 @@ hipError_t launch_merkle_ragged(const uint8_t* base, const uint64_t* offsets, co
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return launch_nodes(n, log2_width, leaves, log2w, roots, expected, matched, stream);
+}
+
+hipError_t launch_merkle_pieces(const uint8_t* base, const uint64_t* offsets, const uint32_t* lens,
+                                const uint8_t* log2w, uint32_t n, uint32_t log2_width, uint8_t* work, uint8_t* roots,
+                                const uint8_t* expected, uint8_t* matched, hipStream_t stream) {
+    if (!roots && !(expected && matched)) return hipSuccess;
+    const uint64_t rows = (uint64_t)n << log2_width;
+    const uint32_t grid = (uint32_t)((rows + kBlock - 1) / kBlock);
+    const bool wide = log2_width > (uint32_t)kPieceTileLog2;
+    const uint32_t top_width = wide ? log2_width - kPieceTileLog2 : 0;
+    uint8_t* log2w_top = wide ? work + ((size_t)n << top_width) * 32 : nullptr;
+    hipLaunchKernelGGL(merkle_piece_kernel, dim3(grid), dim3(kBlock), 0, stream, base, offsets, lens, log2w, n,
+                       log2_width, wide ? work : nullptr, log2w_top, roots, expected, matched);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !wide) return e;
+    return launch_nodes(n, top_width, work, log2w_top, roots, expected, matched, stream);
 }
 
 hipError_t launch_merkle_blocks(const uint8_t* stage, const uint32_t* rows, const uint32_t* lens, uint32_t n_blocks,

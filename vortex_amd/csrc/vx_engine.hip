@@ -3,6 +3,8 @@
 // Replaces, on the host, what vortex does around its hashing pool:
 //  * vx_submit / vx_flush / vx_poll: the scope.spawn → mpsc → try_recv cycle
 //    (peer_connection.rs:1145-1158 → torrent.rs:415-442), batched for the GPU.
+//  * vx_merkle_submit / vx_merkle_poll: the same cycle for a BitTorrent v2
+//    piece (a SHA-256 merkle root), through the same slots and placement.
 //  * vx_sha1_batch / vx_verify_batch: the par_iter bulk verify
 //    (torrent.rs:724-740).
 //  * vx_sha1_device_*: enqueue the kernels on device-resident batches.
@@ -125,6 +127,9 @@ int free_slot_mem(Slot& s) {
     if (s.stream) (void)hipStreamDestroy(s.stream);
     if (s.d_arena) (void)hipFree(s.d_arena);
     if (s.d_meta) (void)hipFree(s.d_meta);
+    if (s.d_v2) (void)hipFree(s.d_v2);
+    if (s.h_v2) (void)hipHostFree(s.h_v2);
+    if (s.d_tops) (void)hipFree(s.d_tops);
     free_stage(s);
     if (s.h_meta) (void)hipHostFree(s.h_meta);
     s = Slot{};
@@ -185,6 +190,27 @@ int ensure_stage(const vx_ctx* c, Slot& s) {
     return 0;
 }
 
+// The v2 buffers of slot s (vx_merkle_submit), allocated on its first v2 piece:
+// a context that only sees v1 pieces allocates nothing for v2.
+int ensure_v2(Slot& s) {
+    if (s.h_v2) return 0;
+    const size_t bytes = (size_t)s.cap * (32 + 32 + 1) + 64;
+    uint8_t *h = nullptr, *d = nullptr;
+    if (hipHostMalloc(&h, bytes, hipHostMallocDefault) != hipSuccess || hipMalloc(&d, bytes) != hipSuccess) {
+        if (h) (void)hipHostFree(h);
+        return fail(VX_ENOMEM, "vx_merkle_submit: v2 metadata allocation failed");
+    }
+    s.h_v2 = h;
+    s.d_v2 = d;
+    s.h_exp32 = h;
+    s.h_roots = h + (size_t)s.cap * 32;
+    s.h_log2w = h + (size_t)s.cap * 64;
+    s.d_exp32 = d;
+    s.d_roots = d + (size_t)s.cap * 32;
+    s.d_log2w = d + (size_t)s.cap * 64;
+    return 0;
+}
+
 void reset_fill(Slot& s) {
     s.tags.clear();
     s.runs.clear();
@@ -198,6 +224,8 @@ void reset_fill(Slot& s) {
     s.uniform = true;
     s.has_expected = false;
     s.use_table = false;
+    s.v2 = false;
+    s.v2_kmax = 0;
     s.all_mapped = true;
 }
 
@@ -355,7 +383,9 @@ int launch_slot_impl(vx_ctx* c, int si) {
     // Zero-copy slot: every piece is read by the hash kernel itself, so no
     // bytes cross PCIe ahead of it and nothing waits for the copy chain.
     // Any slot qualifies, async or inside a host batch (vx_hash.h).
-    const bool zc = s.gtiles && s.all_mapped && c->cfg.zero_copy;
+    // A v2 slot never does: it has no chain for the transfer to hide behind,
+    // so gather-then-hash loses only the hash of one leaf.
+    const bool zc = s.gtiles && s.all_mapped && c->cfg.zero_copy && !s.v2;
     stage_copies(s);
     if (!zc)
         if (int rc = chain_h2d(c, si)) return rc;
@@ -364,7 +394,7 @@ int launch_slot_impl(vx_ctx* c, int si) {
     for (const Run& r : s.runs)
         VX_HIP(hipMemcpyAsync(s.d_arena + r.lo, s.h_stage + r.lo, r.hi - r.lo, hipMemcpyHostToDevice, cs));
     const uint32_t n = s.n;
-    if (!zc && (!s.uniform || s.gtiles)) {
+    if (!zc && (!s.uniform || s.gtiles || s.v2)) {
         VX_HIP(hipMemcpyAsync(s.d_offsets, s.h_offsets, (size_t)n * 8, hipMemcpyHostToDevice, cs));
         VX_HIP(hipMemcpyAsync(s.d_lens, s.h_lens, (size_t)n * 4, hipMemcpyHostToDevice, cs));
     }
@@ -384,7 +414,10 @@ int launch_slot_impl(vx_ctx* c, int si) {
         if (e != hipSuccess) return hip_fail(e, "gather launch");
         c->stats.gather_tiles += s.gtiles;
     }
-    if (s.use_table)
+    if (s.v2) {
+        VX_HIP(hipMemcpyAsync(s.d_log2w, s.h_log2w, n, hipMemcpyHostToDevice, cs));
+        if (s.has_expected) VX_HIP(hipMemcpyAsync(s.d_exp32, s.h_exp32, (size_t)n * 32, hipMemcpyHostToDevice, cs));
+    } else if (s.use_table)
         VX_HIP(hipMemcpyAsync(s.d_pidx, s.h_pidx, (size_t)n * 4, hipMemcpyHostToDevice, cs));
     else if (s.has_expected)
         VX_HIP(hipMemcpyAsync(s.d_expected, s.h_expected, (size_t)n * 20, hipMemcpyHostToDevice, cs));
@@ -393,7 +426,35 @@ int launch_slot_impl(vx_ctx* c, int si) {
     VX_HIP(hipEventRecord(s.copied, cs));
     mark_launched(c, si);
     hipError_t e;
-    if (zc) {
+    if (s.v2) {
+        // The fused piece kernel at the slot's widest tree; above 256 leaves
+        // it leaves tile tops in d_tops and the node kernel follows
+        // (launch_merkle_pieces).
+        const uint32_t K = s.v2_kmax;
+#if VX_MERKLE_ASYNC_FUSED
+        const uint64_t need = K > 8 ? ((uint64_t)n << (K - 8)) * 32 + n : 0;
+#else
+        const uint64_t need = ((uint64_t)n << K) * 32;  // the A/B leg (vx_tuning.h): the leaf + node pair's leaf array
+#endif
+        if (need > s.tops_cap) {
+            if (s.d_tops) (void)hipFree(s.d_tops);
+            s.d_tops = nullptr;
+            s.tops_cap = 0;
+            if (hipMalloc(&s.d_tops, need) != hipSuccess) return fail(VX_ENOMEM, "v2 tile tops allocation failed");
+            s.tops_cap = need;
+        }
+#if VX_MERKLE_ASYNC_FUSED
+        e = vx::launch_merkle_pieces(s.d_arena, s.d_offsets, s.d_lens, s.d_log2w, n, K, s.d_tops, s.d_roots,
+                                     s.has_expected ? s.d_exp32 : nullptr, s.has_expected ? s.d_matched : nullptr,
+                                     s.stream);
+#else
+        e = vx::launch_merkle_ragged(s.d_arena, s.d_offsets, s.d_lens, s.d_log2w, n, K, s.d_tops, s.d_roots,
+                                     s.has_expected ? s.d_exp32 : nullptr, s.has_expected ? s.d_matched : nullptr,
+                                     s.stream);
+#endif
+        if (e != hipSuccess) return hip_fail(e, "merkle piece kernel launch");
+        VX_HIP(hipMemcpyAsync(s.h_roots, s.d_roots, (size_t)n * 32, hipMemcpyDeviceToHost, s.stream));
+    } else if (zc) {
         const bool loader = zc_loader_wins(n);
         e = vx::launch_zero_copy(s.d_src, s.d_lens, n, s.d_digests, d_exp, s.d_matched, loader, s.stream, d_row);
         c->stats.zero_copy_slots++;
@@ -413,7 +474,7 @@ int launch_slot_impl(vx_ctx* c, int si) {
                               s.stream, vx::plan_ragged(n, max_len, total), d_row);
     }
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    VX_HIP(hipMemcpyAsync(s.h_digests, s.d_digests, (size_t)n * 20, hipMemcpyDeviceToHost, s.stream));
+    if (!s.v2) VX_HIP(hipMemcpyAsync(s.h_digests, s.d_digests, (size_t)n * 20, hipMemcpyDeviceToHost, s.stream));
     if (s.has_expected)
         VX_HIP(hipMemcpyAsync(s.h_matched, s.d_matched, n, hipMemcpyDeviceToHost, s.stream));
     VX_HIP(hipEventRecord(s.done, s.stream));
@@ -440,13 +501,22 @@ void record_batch_latency(vx_ctx* c, std::chrono::steady_clock::time_point t_ope
 void harvest(vx_ctx* c, Slot& s) {
     uint64_t bytes = 0, bad = 0;
     for (uint32_t i = 0; i < s.n; ++i) {
-        vx_completion r{};
-        r.tag = s.tags[i];
-        r.matched = s.has_expected ? s.h_matched[i] : 0;
-        std::memcpy(r.digest, s.h_digests + (size_t)i * 20, 20);
-        c->done.push_back(r);
+        const uint8_t matched = s.has_expected ? s.h_matched[i] : 0;
+        if (s.v2) {
+            vx_merkle_completion r{};
+            r.tag = s.tags[i];
+            r.matched = matched;
+            std::memcpy(r.root, s.h_roots + (size_t)i * 32, 32);
+            c->done_v2.push_back(r);
+        } else {
+            vx_completion r{};
+            r.tag = s.tags[i];
+            r.matched = matched;
+            std::memcpy(r.digest, s.h_digests + (size_t)i * 20, 20);
+            c->done.push_back(r);
+        }
         bytes += s.h_lens[i];
-        bad += s.has_expected && !r.matched;
+        bad += s.has_expected && !matched;
     }
     if (s.n) {
         c->stats.pieces_completed += s.n;
@@ -518,8 +588,10 @@ int acquire_filling(vx_ctx* c, bool may_wait = true) {
 
 // piece_row < 0: compare with `expected` (may be NULL); piece_row >= 0:
 // compare with row piece_row of the device piece table.
+// v2_log2w >= 0: a v2 piece (vx_merkle_submit) of 2^v2_log2w leaf slots,
+// `expected` its 32-byte root; placement, ownership and errors are the same.
 int submit_impl(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, const uint8_t* expected,
-                int64_t piece_row) {
+                int64_t piece_row, int v2_log2w) {
     if (c->sticky) return c->sticky;
     if (!data && len) return fail(VX_EINVAL, "vx_submit: data is NULL");
     if (len > c->cfg.max_piece_len) return fail(VX_ERANGE, "vx_submit: piece longer than max_piece_len");
@@ -528,13 +600,18 @@ int submit_impl(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, cons
         return fail(VX_ENOMEM, "vx_submit: injected failure (vx_tuning_fail_submit_after)");
 #endif
     const bool table = piece_row >= 0;
+    const bool v2 = v2_log2w >= 0;
     const bool may_wait = !c->cfg.refuse_when_full || c->bulk;  // host batches always wait
     int si = acquire_filling(c, may_wait);
     if (si < 0) return si;
     Slot* s = &c->slots[si];
     uint64_t off = align_up(s->bytes, kAlign);
-    // a slot holds either table-indexed or explicit-digest pieces
-    if (s->n == s->cap || off + len > s->arena_cap || (s->n && s->use_table != table)) {
+    // the piece kernel runs (pieces << widest log2w) lanes, a 32-bit count
+    const bool v2_lanes_full =
+        v2 && ((uint64_t)(s->n + 1) << std::max<uint32_t>(s->v2_kmax, (uint32_t)v2_log2w)) > (1ull << 31);
+    // a slot holds either table-indexed or explicit-digest pieces, and either v1 or v2 pieces
+    if (s->n == s->cap || off + len > s->arena_cap || (s->n && (s->use_table != table || s->v2 != v2)) ||
+        (s->n && v2_lanes_full)) {
         int rc = launch_slot(c, si);
         if (rc) return rc;
         si = acquire_filling(c, may_wait);
@@ -544,6 +621,8 @@ int submit_impl(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, cons
     }
     const uint32_t i = s->n;
     const uint8_t* dev = nullptr;
+    if (v2)
+        if (int rc = ensure_v2(*s)) return rc;
     s->h_src[i] = 0;
     if (i == 0) s->t_open = std::chrono::steady_clock::now();
     if (len && (reinterpret_cast<uintptr_t>(data) & 15) == 0 && is_registered(c, data, len, &dev)) {
@@ -587,20 +666,28 @@ int submit_impl(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, cons
     // Equal lengths at 256-byte aligned back-to-back offsets are a uniform
     // batch: offset(i) = i * align_up(len, 256) (the uniform kernel's layout).
     if (i > 0 && len != s->h_lens[0]) s->uniform = false;
+    // a v2 piece's expected row is its 32-byte root, in the slot's v2 block
+    const size_t dlen = v2 ? 32 : 20;
+    uint8_t* h_exp = v2 ? s->h_exp32 : s->h_expected;
+    if (v2) {
+        s->v2 = true;
+        s->h_log2w[i] = (uint8_t)v2_log2w;
+        s->v2_kmax = std::max<uint32_t>(s->v2_kmax, (uint32_t)v2_log2w);
+    }
     if (table) {
         s->h_pidx[i] = (uint32_t)piece_row;
         s->use_table = true;
         s->has_expected = true;
     } else if (expected) {
-        std::memcpy(s->h_expected + (size_t)i * 20, expected, 20);
+        std::memcpy(h_exp + (size_t)i * dlen, expected, dlen);
         if (i > 0 && !s->has_expected) {
             // earlier pieces of this batch had no expected digest: they get
             // matched = 0 against a zero table, which nobody reads.
-            std::memset(s->h_expected, 0, (size_t)i * 20);
+            std::memset(h_exp, 0, (size_t)i * dlen);
         }
         s->has_expected = true;
     } else if (s->has_expected) {
-        std::memset(s->h_expected + (size_t)i * 20, 0, 20);
+        std::memset(h_exp + (size_t)i * dlen, 0, dlen);
     }
     s->tags.push_back(tag);
     s->n = i + 1;
@@ -846,6 +933,34 @@ void abandon_batch(vx_ctx* c) {
     c->pending = 0;
 }
 
+// vx_poll / vx_merkle_poll: harvest what has finished (slots of either kind),
+// then hand out the caller's kind from its own queue.
+template <class Completion>
+int64_t poll_impl(vx_ctx* c, std::deque<Completion>& done, Completion* out, size_t max) {
+    int rc = set_device(c);
+    if (rc) return rc;
+    if (c->sticky) {
+        // Failed context: hand out every result the device did produce (batches
+        // that finished, harvested now or earlier), then the error.  The tags
+        // never returned are the pieces to re-hash elsewhere (INTEGRATION.md).
+        const int sticky = c->sticky;
+        (void)reap(c, false);
+        c->sticky = sticky;
+        if (done.empty()) return sticky;
+    } else {
+        rc = reap(c, false);
+        if (rc) return rc;
+        if (c->flush_pending && c->filling >= 0 && may_launch_now(c) && (rc = launch_slot(c, c->filling))) return rc;
+    }
+    size_t k = 0;
+    while (k < max && !done.empty()) {
+        out[k++] = done.front();
+        done.pop_front();
+    }
+    c->pending -= k;
+    return (int64_t)k;
+}
+
 }  // namespace vxe
 
 using namespace vxe;
@@ -1062,28 +1177,28 @@ int vx_flush(vx_ctx* c) {
 
 int64_t vx_poll(vx_ctx* c, vx_completion* out, size_t max) {
     if (!c || (!out && max)) return fail(VX_EINVAL, "vx_poll: bad argument");
+    return poll_impl(c, c->done, out, max);
+}
+
+int64_t vx_merkle_poll(vx_ctx* c, vx_merkle_completion* out, size_t max) {
+    if (!c || (!out && max)) return fail(VX_EINVAL, "vx_merkle_poll: bad argument");
+    return poll_impl(c, c->done_v2, out, max);
+}
+
+int vx_merkle_submit(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, uint32_t log2w,
+                     const uint8_t* expected) {
+    if (!c) return fail(VX_EINVAL, "vx_merkle_submit: NULL context");
+    if (len > c->cfg.max_piece_len) return fail(VX_ERANGE, "vx_merkle_submit: piece longer than max_piece_len");
+    if (log2w > VX_MERKLE_MAX_LOG2_WIDTH) return fail(VX_EINVAL, "vx_merkle_submit: log2w > 17");
+    if (len > (uint64_t)VX_MERKLE_BLOCK << log2w)
+        return fail(VX_EINVAL, "vx_merkle_submit: piece longer than its tree (16384 << log2w)");
+    uint64_t widest = VX_MERKLE_BLOCK;  // max_piece_len rounded up to a power of two
+    while (widest < c->cfg.max_piece_len) widest <<= 1;
+    if (((uint64_t)VX_MERKLE_BLOCK << log2w) > widest)
+        return fail(VX_EINVAL, "vx_merkle_submit: tree wider than max_piece_len");
     int rc = set_device(c);
     if (rc) return rc;
-    if (c->sticky) {
-        // Failed context: hand out every result the device did produce (batches
-        // that finished, harvested now or earlier), then the error.  The tags
-        // never returned are the pieces to re-hash elsewhere (INTEGRATION.md).
-        const int sticky = c->sticky;
-        (void)reap(c, false);
-        c->sticky = sticky;
-        if (c->done.empty()) return sticky;
-    } else {
-        rc = reap(c, false);
-        if (rc) return rc;
-        if (c->flush_pending && c->filling >= 0 && may_launch_now(c) && (rc = launch_slot(c, c->filling))) return rc;
-    }
-    size_t k = 0;
-    while (k < max && !c->done.empty()) {
-        out[k++] = c->done.front();
-        c->done.pop_front();
-    }
-    c->pending -= k;
-    return (int64_t)k;
+    return submit_impl(c, tag, data, len, expected, -1, (int)log2w);
 }
 
 int vx_drain(vx_ctx* c, uint32_t timeout_ms) {

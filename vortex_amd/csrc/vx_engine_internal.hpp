@@ -97,6 +97,21 @@ struct Slot {
     uint8_t* d_expected = nullptr;
     uint8_t* d_digests = nullptr;
     uint8_t* d_matched = nullptr;
+    // v2 pieces (vx_merkle_submit), allocated on the slot's first v2 use
+    // (ensure_v2): a pinned and a device block of expected roots (32 cap) |
+    // roots (32 cap) | log2w (cap); the verdicts share h_matched / d_matched.
+    uint8_t* h_v2 = nullptr;
+    uint8_t* d_v2 = nullptr;
+    uint8_t* h_exp32 = nullptr;
+    uint8_t* h_roots = nullptr;
+    uint8_t* h_log2w = nullptr;
+    uint8_t* d_exp32 = nullptr;
+    uint8_t* d_roots = nullptr;
+    uint8_t* d_log2w = nullptr;
+    // the piece kernel's work area for trees wider than 256 leaves (tile tops |
+    // their log2w), grown when a launch needs more
+    uint8_t* d_tops = nullptr;
+    uint64_t tops_cap = 0;
     std::vector<uint64_t> tags;
     std::vector<Run> runs;
     std::vector<DirectRun> druns;
@@ -107,6 +122,8 @@ struct Slot {
     bool uniform = true;
     bool has_expected = false;
     bool use_table = false;  // expected digests come from the device piece table
+    bool v2 = false;         // the slot's pieces are v2 (vx_merkle_submit): a slot holds one kind
+    uint32_t v2_kmax = 0;    // ... and their widest log2w: the piece kernel runs n << v2_kmax lanes
     bool all_mapped = true;  // every non-empty piece is registered and 16-byte aligned (zero-copy candidate)
     enum State { FREE, FILLING, INFLIGHT } state = FREE;
     uint64_t seq = 0;
@@ -140,6 +157,7 @@ struct vx_ctx {
     bool flush_pending = false;
     bool bulk = false;  // inside vx_*_batch: slots fill to capacity, not to batch_pieces
     std::deque<vx_completion> done;
+    std::deque<vx_merkle_completion> done_v2;  // v2 pieces' results (vx_merkle_poll)
     struct Reg {
         size_t len;
         uint8_t* dev;  // device mapping of the range (hipHostGetDevicePointer)
@@ -289,7 +307,7 @@ void mark_launched(vx_ctx* c, int si);
 int launch_slot(vx_ctx* c, int si);
 int reap(vx_ctx* c, bool block_oldest);
 int submit_impl(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, const uint8_t* expected,
-                int64_t piece_row = -1);
+                int64_t piece_row = -1, int v2_log2w = -1);
 void abandon_batch(vx_ctx* c);
 void release_filling_slots(vx_ctx* c);   // every FILLING slot (reserved, never launched) back to FREE
 void wait_and_free_inflight(vx_ctx* c);  // wait for every INFLIGHT slot, then free them unharvested

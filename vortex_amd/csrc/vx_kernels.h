@@ -93,6 +93,14 @@ hipError_t launch_merkle_uniform(const uint8_t* base, uint64_t stride, uint32_t 
 hipError_t launch_merkle_ragged(const uint8_t* base, const uint64_t* offsets, const uint32_t* lens,
                                 const uint8_t* log2w, uint32_t n, uint32_t log2_width, uint8_t* leaves,
                                 uint8_t* roots, const uint8_t* expected, uint8_t* matched, hipStream_t stream);
+// The fused piece kernel (the async path): as launch_merkle_ragged, but the
+// leaf rows stay in LDS and are not kept.  log2_width <= 8: one launch, work
+// unused.  Wider: work = tile tops ((n << (log2_width-8)) * 32 bytes) | log2w
+// of the tops' trees (n bytes), both written by the piece kernel, then the
+// node kernel over the tops.
+hipError_t launch_merkle_pieces(const uint8_t* base, const uint64_t* offsets, const uint32_t* lens,
+                                const uint8_t* log2w, uint32_t n, uint32_t log2_width, uint8_t* work, uint8_t* roots,
+                                const uint8_t* expected, uint8_t* matched, hipStream_t stream);
 // The two halves on their own (the re-verify from disk): the block kernel
 // hashes stage block b (lens[b] <= 16384 bytes at stage + b*16384) into leaf
 // row rows[b] (0xFFFFFFFF: none; lens[b] == 0: the zero hash, nothing read);

@@ -139,6 +139,29 @@ int vx_merkle_device_ragged(const void* d_base, const uint64_t* d_offsets, const
     return 0;
 }
 
+int vx_merkle_device_pieces(const void* d_base, const uint64_t* d_offsets, const uint32_t* d_lens,
+                            const uint8_t* d_log2w, uint32_t n, uint32_t log2_width, void* d_work, void* d_roots,
+                            const void* d_expected, void* d_matched, void* stream) {
+    if (n == 0) return 0;
+    // (d_base stands in for the leaf array merkle_args also checks: this entry has none)
+    int rc = merkle_args("vx_merkle_device_pieces", d_base, d_base, n, log2_width);
+    if (rc) return rc;
+    if (!d_offsets || !d_lens) return fail(VX_EINVAL, "vx_merkle_device_pieces: NULL d_offsets or d_lens");
+    if ((reinterpret_cast<uintptr_t>(d_roots) & 15) || (reinterpret_cast<uintptr_t>(d_expected) & 3))
+        return fail(VX_EINVAL, "vx_merkle_device_pieces: d_roots must be 16-byte and d_expected 4-byte aligned");
+    if (log2_width > 8 && (!d_work || (reinterpret_cast<uintptr_t>(d_work) & 15)))
+        return fail(VX_EINVAL, "vx_merkle_device_pieces: log2_width > 8 needs a 16-byte aligned d_work");
+    const bool verdict = d_expected && d_matched;
+    hipError_t e = vx::launch_merkle_pieces(static_cast<const uint8_t*>(d_base), d_offsets, d_lens, d_log2w, n,
+                                            log2_width, static_cast<uint8_t*>(d_work),
+                                            static_cast<uint8_t*>(d_roots),
+                                            verdict ? static_cast<const uint8_t*>(d_expected) : nullptr,
+                                            verdict ? static_cast<uint8_t*>(d_matched) : nullptr,
+                                            static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "merkle piece kernel launch");
+    return 0;
+}
+
 int vx_merkle_device_root(const void* d_layer, uint32_t n, uint32_t height, void* d_work, void* d_root,
                           void* stream) {
     if (n == 0) return 0;

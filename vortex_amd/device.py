@@ -169,14 +169,17 @@ def sha1_ragged(data: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor,
     return digests, matched
 
 
-def _merkle_outputs(n: int, log2_width: int, dev, expected, leaves, roots, matched):
-    """Allocate / check the output tensors of a merkle call."""
+def _merkle_outputs(n: int, log2_width: int, dev, expected, leaves, roots, matched, want_leaves: bool = True):
+    """Allocate / check the output tensors of a merkle call (want_leaves
+    False: a call that keeps no leaf layer; `leaves` comes back as given)."""
     if not 0 <= log2_width <= 17:
         raise ValueError("log2_width must be 0..17")
     rows = n << log2_width
     if rows >> 32:
         raise ValueError("n << log2_width must fit 32 bits")
-    if leaves is None:
+    if not want_leaves:
+        pass
+    elif leaves is None:
         leaves = torch.empty((rows, 32), dtype=torch.uint8, device=dev)
     else:
         _req(leaves, "leaves")
@@ -230,7 +233,7 @@ def merkle_uniform(data: torch.Tensor, n: int, piece_len: int, log2_width: int, 
 
 
 def _check_merkle_layout(data: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor,
-                         log2w: Optional[torch.Tensor], log2_width: int) -> None:
+                         log2w: Optional[torch.Tensor], log2_width: int, who: str = "merkle_ragged") -> None:
     """What :func:`_check_ragged_layout` checks for sha1_ragged, for a merkle
     batch: offsets 16-byte aligned and >= 0, lengths >= 0, every piece inside
     `data`, every log2w <= log2_width and every piece inside its own tree
@@ -247,16 +250,16 @@ def _check_merkle_layout(data: torch.Tensor, offsets: torch.Tensor, lens: torch.
         (lens.to(torch.int64) > torch.bitwise_left_shift(torch.full_like(lw, 16384), lw.clamp(0, 17))).any().to(torch.int64),
     ]).cpu().tolist()
     if stats[0]:
-        raise ValueError("merkle_ragged: every offset must be a multiple of 16 (the kernels load 16 bytes per lane)")
+        raise ValueError(f"{who}: every offset must be a multiple of 16 (the kernels load 16 bytes per lane)")
     if stats[1]:
-        raise ValueError("merkle_ragged: negative offset or length")
+        raise ValueError(f"{who}: negative offset or length")
     if stats[2] > data.numel():
-        raise ValueError(f"merkle_ragged: a piece ends at byte {stats[2]}, past the data tensor "
+        raise ValueError(f"{who}: a piece ends at byte {stats[2]}, past the data tensor "
                          f"({data.numel()} bytes)")
     if stats[3] > log2_width:
-        raise ValueError(f"merkle_ragged: log2w {stats[3]} > log2_width {log2_width}")
+        raise ValueError(f"{who}: log2w {stats[3]} > log2_width {log2_width}")
     if stats[4]:
-        raise ValueError("merkle_ragged: a piece is longer than its tree (16384 << log2w bytes)")
+        raise ValueError(f"{who}: a piece is longer than its tree (16384 << log2w bytes)")
 
 
 def merkle_ragged(data: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor, log2_width: int,
@@ -296,6 +299,49 @@ def merkle_ragged(data: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor,
                                        _stream_ptr(stream, dev))
     check(rc, "vx_merkle_device_ragged")
     return roots, leaves, matched
+
+
+def merkle_pieces(data: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor, log2_width: int,
+                  log2w: Optional[torch.Tensor] = None, expected: Optional[torch.Tensor] = None,
+                  roots: Optional[torch.Tensor] = None, matched: Optional[torch.Tensor] = None,
+                  stream: Optional[torch.cuda.Stream] = None, validate: bool = True):
+    """The batch of :func:`merkle_ragged` through the fused piece kernel
+    (vx_merkle_device_pieces), which keeps no leaf layer: the leaf rows are
+    reduced in LDS.  One launch for log2_width <= 8; above, a work tensor of
+    (n << (log2_width - 8)) * 32 + n bytes is allocated here and a node launch
+    follows.  Arguments and layout checks as for merkle_ragged.
+
+    Returns (roots [n,32], matched [n] or None)."""
+    _req(data, "data")
+    _req(offsets, "offsets", torch.int64)
+    _req(lens, "lens", torch.int32)
+    n = offsets.numel()
+    if lens.numel() != n:
+        raise ValueError("offsets and lens differ in length")
+    if log2w is not None:
+        _req(log2w, "log2w")
+        if log2w.numel() != n:
+            raise ValueError("log2w must hold n widths")
+    dev = data.device
+    for name, t in (("offsets", offsets), ("lens", lens), ("log2w", log2w)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, data on {dev}")
+    _, roots, matched = _merkle_outputs(n, log2_width, dev, expected, None, roots, matched, want_leaves=False)
+    if validate:
+        _check_merkle_layout(data, offsets, lens, log2w, log2_width, "merkle_pieces")
+    work = None
+    if log2_width > 8 and n:
+        work = torch.empty(((n << (log2_width - 8)) * 32 + n,), dtype=torch.uint8, device=dev)
+        if stream is not None:  # the scratch outlives this call on the stream that uses it
+            work.record_stream(stream)
+    rc = lib().vx_merkle_device_pieces(data.data_ptr(), offsets.data_ptr(), lens.data_ptr(),
+                                       log2w.data_ptr() if log2w is not None else None, n, log2_width,
+                                       work.data_ptr() if work is not None else None, roots.data_ptr(),
+                                       expected.data_ptr() if expected is not None else None,
+                                       matched.data_ptr() if matched is not None else None,
+                                       _stream_ptr(stream, dev))
+    check(rc, "vx_merkle_device_pieces")
+    return roots, matched
 
 
 SKIP_ROW = 0xFFFFFFFF  # merkle_blocks: a block that stores no leaf row

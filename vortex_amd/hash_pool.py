@@ -15,6 +15,10 @@ reference                        here
   torrent.rs:724-740
 ===============================  ==============================================
 
+A BitTorrent v2 (BEP 52) piece takes the same path under
+:meth:`HashPool.spawn_merkle` / :meth:`HashPool.try_recv_merkle`: its result is
+the piece's SHA-256 merkle root (vx_merkle_submit / vx_merkle_poll).
+
 Semantics kept from the reference:
 * a hash mismatch is a value (``hash_matched=False``), never an exception;
 * the buffer is moved into the job and handed back in ``DownloadedPiece``
@@ -108,6 +112,7 @@ class HashPool:
         self._next_tag = 0
         self._inflight: dict[int, tuple[int, int, Any, Any]] = {}
         self._cbuf = (vx_completion * 1024)()
+        self._cbuf_v2 = (_lib.vx_merkle_completion * 1024)()
         self._registered: dict[int, tuple[int, Any, Any]] = {}  # id(buf) -> (address, keep-alive, buf)
 
     # -- lifecycle ---------------------------------------------------------
@@ -183,6 +188,37 @@ class HashPool:
                 raise
         self._inflight[tag] = (index, conn_id, buffer, keep)
 
+    def spawn_merkle(self, index: int, conn_id: int, buffer, piece_len: int,
+                     expected_root: Optional[bytes] = None, log2w: Optional[int] = None) -> None:
+        """spawn() for a BitTorrent v2 (BEP 52) piece (vx_merkle_submit): the
+        SHA-256 merkle root of buffer[:piece_len] over 16 KiB blocks, as a
+        tree of 2^log2w leaf slots (default: piece_length / 16 KiB, the width
+        of every piece of a file longer than piece_length; merkle.file_pieces
+        gives the width of a short file's single piece), compared with
+        expected_root (32 bytes; None: the root is only returned).  The result
+        comes back from try_recv_merkle() / try_iter_merkle(), never from
+        try_recv().  Ownership and errors as for spawn()."""
+        if expected_root is not None and len(expected_root) != 32:
+            raise ValueError("expected_root must be 32 bytes")
+        if log2w is None:
+            log2w = max(0, (int(self.config.max_piece_len) // _lib.VX_MERKLE_BLOCK).bit_length() - 1)
+        if not 0 <= int(log2w) < 1 << 32:
+            raise ValueError("log2w outside the uint32 range")
+        addr, keep = _addr_of(buffer)
+        if piece_len > memoryview(buffer).nbytes:
+            raise ValueError("piece_len exceeds buffer size")
+        tag = self._next_tag
+        self._next_tag += 1
+        exp = ctypes.create_string_buffer(bytes(expected_root), 32) if expected_root is not None else None
+        rc = self.lib.vx_merkle_submit(self._h, tag, addr, piece_len, int(log2w), exp)
+        if rc != 0:
+            try:
+                check(rc, "vx_merkle_submit", self.lib)
+            except VxError as e:
+                e.refused = (index, conn_id, buffer)
+                raise
+        self._inflight[tag] = (index, conn_id, buffer, keep)
+
     def set_piece_table(self, pieces: bytes) -> None:
         """Upload the torrent's `pieces` string (n x 20 B) once; afterwards
         spawn(..., expected_hash=None) compares on the device by index."""
@@ -223,8 +259,39 @@ class HashPool:
             if len(got) < len(self._cbuf):
                 return out
 
+    def _poll_merkle(self, max_items: int) -> list[DownloadedPiece]:
+        k = check(self.lib.vx_merkle_poll(self._h, self._cbuf_v2, min(max_items, len(self._cbuf_v2))),
+                  "vx_merkle_poll", self.lib)
+        out = []
+        for j in range(k):
+            r = self._cbuf_v2[j]
+            index, conn_id, buffer, _keep = self._inflight.pop(r.tag)
+            out.append(DownloadedPiece(index, conn_id, bool(r.matched), buffer, bytes(r.root)))
+        return out
+
+    def try_recv_merkle(self) -> Optional[DownloadedPiece]:
+        """try_recv() for v2 pieces (vx_merkle_poll): `digest` is the 32-byte
+        merkle root.  Pieces given to spawn() never arrive here."""
+        got = self._poll_merkle(1)
+        return got[0] if got else None
+
+    def try_iter_merkle(self) -> list[DownloadedPiece]:
+        """Every v2 piece completed so far (try_iter() for spawn_merkle)."""
+        out = []
+        while True:
+            try:
+                got = self._poll_merkle(len(self._cbuf_v2))
+            except VxError:
+                if out:  # as try_iter: the error is sticky and the next call raises it
+                    return out
+                raise
+            out.extend(got)
+            if len(got) < len(self._cbuf_v2):
+                return out
+
     def take_unfinished(self) -> list[tuple[int, int, Any]]:
-        """After a device error (a VxError from spawn / try_recv / try_iter):
+        """After a device error (a VxError from spawn / try_recv / try_iter, or
+        their _merkle forms; pieces of both kinds are listed):
         (index, conn_id, buffer) of every TAKEN piece whose result never came
         back, for the caller to hash on its own pool (INTEGRATION.md "Device
         failure").  A spawn that raised did not take its piece (it is in the
