@@ -637,6 +637,108 @@ int64_t vx_merkle_verify_files_range(vx_ctx* ctx, const char* const* paths, cons
                                      size_t nfiles, uint32_t piece_length, const uint8_t* expected, size_t n_pieces,
                                      size_t first, size_t count, uint8_t* matched_out, uint32_t io_threads);
 
+/* ---- v2 metadata: `piece layers` and hash proofs in batches -------------
+ * Every entry above takes its expected rows on trust.  BEP 52 says how a
+ * client earns that trust: a file's `piece layers` string must reduce to the
+ * file's `pieces root` (padded to a power of two with pad hashes), and a layer
+ * that arrives over the wire comes in `hashes` messages, a span of consecutive
+ * hashes of one layer followed by the uncle hashes that lead from the span's
+ * root to `pieces root` or to an ancestor already trusted.
+ *
+ * Segmented layer roots: many layers of different sizes, all `height` levels
+ * above the leaves (log2(piece_length / VX_MERKLE_BLOCK) for `piece layers`),
+ * back to back in one buffer: layer f is counts[f] rows of 32 bytes.  The sizes
+ * follow from the file lengths, so the host plans and the device only executes
+ * (as for vx_sort_order).  A layer of m rows still alive at pass p is cut into
+ * tiles of VX_MERKLE_TILE_ROWS rows, one workgroup each: m <= 512 is one last
+ * tile of ceil(log2 m) levels whose top is the layer's root; otherwise every
+ * tile reduces 9 levels (the short last tile filled with the pass's pad hash)
+ * into a row of d_work, and those rows are the layer at pass p + 1.  Every
+ * input row of pass p stands at height + 9p. */
+#define VX_MERKLE_TILE_ROWS 512
+typedef struct vx_merkle_tile { /* one workgroup in one pass; 16 bytes */
+    uint32_t in_row; /* first input row: pass 0 a row of d_hashes, later passes a row of d_work        */
+    uint32_t out;    /* last == 0: the row of d_work it writes; last == 1: the layer whose root this is */
+    uint16_t rows;   /* 1..512 rows that exist; the tile is filled to 1 << levels with the pass's pad   */
+    uint8_t levels;  /* 0..9 (0: the layer is one hash, its root is that hash)                          */
+    uint8_t last;
+    uint32_t _pad;
+} vx_merkle_tile;
+/* (No typedef: in C it would collide with the function of the same name, so
+ * the struct is named by its tag, as `struct stat` beside stat().) */
+struct vx_merkle_layers_plan {
+    uint32_t n_layers, passes;       /* passes 0..4 */
+    uint64_t rows;                   /* sum of counts */
+    uint64_t work_rows;              /* 32-byte rows d_work must hold */
+    uint32_t n_tiles, pass_tiles[4]; /* tiles of pass p lie consecutively, pass after pass */
+    uint32_t _pad;
+};
+/* Plan n_layers layers of counts[f] >= 1 rows; host only.  tiles == NULL fills
+ * *plan only, so the caller can size its buffers; otherwise tiles[0..n_tiles)
+ * are written.  VX_EINVAL: a count of 0, a sum of counts of 2^32 or more, or
+ * tiles given with tiles_cap < n_tiles (then nothing is written to tiles). */
+int vx_merkle_layers_plan(const uint32_t* counts, uint32_t n_layers, struct vx_merkle_layers_plan* plan,
+                          vx_merkle_tile* tiles, size_t tiles_cap);
+/* Execute a plan: plan->passes launches whatever n_layers is (n_layers == 0
+ * launches nothing).  d_hashes: plan->rows rows, not modified; d_tiles: a
+ * device copy of the planner's tiles; d_work: plan->work_rows rows (may be
+ * NULL when that is 0).  d_roots (n_layers * 32 bytes, may be NULL) gets the
+ * roots; with d_expected and d_matched both given, d_matched[f] = (root ==
+ * d_expected[32*f..]).  height <= 64; d_hashes, d_work and d_roots 16-byte,
+ * d_tiles and d_expected 4-byte aligned.  The tiles are device-resident and
+ * not checked here.  Enqueue-only. */
+int vx_merkle_device_layers(const void* d_hashes, const struct vx_merkle_layers_plan* plan,
+                            const vx_merkle_tile* d_tiles, uint32_t height, void* d_work, void* d_roots,
+                            const void* d_expected, void* d_matched, void* stream);
+
+/* One `hashes` message (BEP 52), or the part of one a client checks at once:
+ * `span` consecutive hashes of a layer and the uncles above them.  With
+ * base layer 0 the span is a piece's leaf hashes and the result the piece's
+ * row of `piece layers`: how a client finds the bad 16 KiB block of a failed
+ * piece. */
+typedef struct vx_merkle_proof { /* 24 bytes */
+    uint64_t pos;      /* which span of its size in its layer (wire: index / length); bit k set: at step k the
+                          running hash is the right child, node = H(uncle_k || cur); clear: H(cur || uncle_k) */
+    uint32_t row;      /* first row of this proof in d_hashes: span rows, then uncles rows, as on the wire     */
+    uint32_t expected; /* the row of d_expected the result must equal (many proofs share one root)             */
+    uint16_t span;     /* a power of two, 1..512 */
+    uint8_t uncles;    /* 0..64: the hashes behind the span in the message (its `proof layers` field is not used) */
+    uint8_t _pad[5];
+} vx_merkle_proof;
+/* Verify n proofs in two launches: one workgroup per proof reduces its span to
+ * the span's root (d_tops[32*i..], also the hand-over between the launches),
+ * then one lane per proof walks the uncles, leaves the top in d_tops and sets
+ * d_matched[i] = (top == d_expected[32 * expected..]).  d_tops (n * 32 bytes)
+ * and d_matched (n bytes) are required.  The proofs are device-resident and
+ * not checked here, but the kernels do not trust them: a span that is not a
+ * power of two in 1..512 or uncles > 64 gives d_matched[i] = 0 and an all-zero
+ * top, and none of that proof's rows are read.  row and expected are the
+ * caller's to bound (vx_merkle_verify_proofs does).  d_hashes and d_tops
+ * 16-byte, d_proofs 8-byte, d_expected 4-byte aligned.  Enqueue-only; n == 0
+ * launches nothing. */
+int vx_merkle_device_proofs(const void* d_hashes, const vx_merkle_proof* d_proofs, uint32_t n, void* d_tops,
+                            const void* d_expected, void* d_matched, void* stream);
+
+/* The two on a context, for hashes in host memory; both synchronous, on a
+ * stream and device buffers of their own (allocated per call: this runs once
+ * per torrent or per batch of messages, not per piece).  Neither touches the
+ * batch slots, the pending count or vx_get_stats, and neither returns VX_EBUSY
+ * while async pieces are pending: proofs for one file arrive while another
+ * file's pieces download.
+ * vx_merkle_verify_layers: hashes = the layers back to back (sum of counts
+ * rows), expected = n_layers `pieces root` rows; matched_out[f] = 0/1;
+ * roots_out (may be NULL) gets n_layers * 32 bytes. */
+int vx_merkle_verify_layers(vx_ctx* ctx, const uint8_t* hashes, const uint32_t* counts, uint32_t n_layers,
+                            uint32_t height, const uint8_t* expected, uint8_t* matched_out, uint8_t* roots_out);
+/* vx_merkle_verify_proofs: hashes = n_rows rows holding every proof's span and
+ * uncles, expected = n_expected trusted rows; matched_out[i] = 0/1; tops_out
+ * (may be NULL) gets n * 32 bytes.  Each proof is checked first: span a power
+ * of two of at most 512, uncles <= 64, row + span + uncles <= n_rows, expected
+ * < n_expected; VX_EINVAL with the first bad index in vx_last_error. */
+int vx_merkle_verify_proofs(vx_ctx* ctx, const uint8_t* hashes, uint64_t n_rows, const vx_merkle_proof* proofs,
+                            uint32_t n, const uint8_t* expected, uint32_t n_expected, uint8_t* matched_out,
+                            uint8_t* tops_out);
+
 #ifdef __cplusplus
 }
 #endif

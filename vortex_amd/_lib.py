@@ -54,6 +54,8 @@ EXPORTS = (
     "vx_merkle_verify_batch",
     "vx_merkle_device_blocks", "vx_merkle_device_nodes", "vx_merkle_verify_files", "vx_merkle_verify_files_range",
     "vx_merkle_device_pieces", "vx_merkle_submit", "vx_merkle_poll",
+    "vx_merkle_layers_plan", "vx_merkle_device_layers", "vx_merkle_device_proofs", "vx_merkle_verify_layers",
+    "vx_merkle_verify_proofs",
 )
 # ... plus include/vx_tuning.h and include/vx_synth.h: libvortex_amd_tuning.so only.
 TUNING_EXPORTS = (
@@ -83,6 +85,43 @@ class vx_merkle_completion(ctypes.Structure):
     """A v2 piece's completion (vx_merkle_poll): 48 bytes."""
     _fields_ = [("tag", ctypes.c_uint64), ("matched", ctypes.c_uint8), ("root", ctypes.c_uint8 * 32),
                 ("_pad", ctypes.c_uint8 * 7)]
+
+
+VX_MERKLE_TILE_ROWS = 512
+
+
+class vx_merkle_tile(ctypes.Structure):
+    """One workgroup in one pass of vx_merkle_device_layers: 16 bytes."""
+    _fields_ = [("in_row", ctypes.c_uint32), ("out", ctypes.c_uint32), ("rows", ctypes.c_uint16),
+                ("levels", ctypes.c_uint8), ("last", ctypes.c_uint8), ("_pad", ctypes.c_uint32)]
+
+
+class vx_merkle_layers_plan(ctypes.Structure):
+    """What vx_merkle_layers_plan (the function) fills: 48 bytes.  In C the
+    struct goes by its tag, `struct vx_merkle_layers_plan`."""
+    _fields_ = [("n_layers", ctypes.c_uint32), ("passes", ctypes.c_uint32), ("rows", ctypes.c_uint64),
+                ("work_rows", ctypes.c_uint64), ("n_tiles", ctypes.c_uint32), ("pass_tiles", ctypes.c_uint32 * 4),
+                ("_pad", ctypes.c_uint32)]
+
+
+class vx_merkle_proof(ctypes.Structure):
+    """One hash proof (a BEP 52 `hashes` message): 24 bytes."""
+    _fields_ = [("pos", ctypes.c_uint64), ("row", ctypes.c_uint32), ("expected", ctypes.c_uint32),
+                ("span", ctypes.c_uint16), ("uncles", ctypes.c_uint8), ("_pad", ctypes.c_uint8 * 5)]
+
+
+def proof_array(proofs):
+    """A host sequence of proofs, each (pos, row, expected, span, uncles) or a
+    vx_merkle_proof, as a ctypes array; ValueError when a number does not fit
+    its field (ctypes would cut it silently)."""
+    arr = (vx_merkle_proof * max(len(proofs), 1))()
+    widths = (64, 32, 32, 16, 8)
+    for i, p in enumerate(proofs):
+        v = (p.pos, p.row, p.expected, p.span, p.uncles) if isinstance(p, vx_merkle_proof) else tuple(int(x) for x in p)
+        if len(v) != 5 or any(not 0 <= x < 1 << w for x, w in zip(v, widths)):
+            raise ValueError(f"proof {i}: (pos, row, expected, span, uncles) = {v} does not fit vx_merkle_proof")
+        arr[i].pos, arr[i].row, arr[i].expected, arr[i].span, arr[i].uncles = v
+    return arr
 
 
 ABI_VERSION = 3
@@ -209,6 +248,12 @@ def _declare(L: ctypes.CDLL, tuning: bool = False) -> None:
         "vx_merkle_device_pieces": ([vp, vp, vp, vp, c.c_uint32, c.c_uint32, vp, vp, vp, vp, vp], c.c_int),
         "vx_merkle_submit": ([vp, c.c_uint64, vp, c.c_uint32, c.c_uint32, vp], c.c_int),
         "vx_merkle_poll": ([vp, c.POINTER(vx_merkle_completion), c.c_size_t], c.c_int64),
+        "vx_merkle_layers_plan": ([vp, c.c_uint32, c.POINTER(vx_merkle_layers_plan), vp, c.c_size_t], c.c_int),
+        "vx_merkle_device_layers": ([vp, c.POINTER(vx_merkle_layers_plan), vp, c.c_uint32, vp, vp, vp, vp, vp],
+                                    c.c_int),
+        "vx_merkle_device_proofs": ([vp, vp, c.c_uint32, vp, vp, vp, vp], c.c_int),
+        "vx_merkle_verify_layers": ([vp, vp, vp, c.c_uint32, c.c_uint32, vp, vp, vp], c.c_int),
+        "vx_merkle_verify_proofs": ([vp, vp, c.c_uint64, vp, c.c_uint32, vp, c.c_uint32, vp, vp], c.c_int),
     }
     if tuning:
         sig.update({

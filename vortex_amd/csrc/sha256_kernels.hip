@@ -20,6 +20,11 @@
 //    piece tile by tile and then the tiles' tops.  Under 1 % of the leaf work.
 //  * layer kernel (vx_merkle_device_root): the same tile reduction over a
 //    layer of n hashes, missing rows filled with the pad hash of the level.
+//  * layers kernel (vx_merkle_device_layers): that reduction over many layers
+//    at once, one workgroup per tile of a plan the host made
+//    (vx_merkle_layers.hpp), one launch per pass.
+//  * proof kernels (vx_merkle_device_proofs): a workgroup per proof reduces its
+//    span in the same tile, then a lane per proof walks the uncles.
 //  * piece kernel (vx_merkle_device_pieces, the async path of
 //    vx_merkle_submit): the leaf kernel's lanes with the tree fused on.  A
 //    workgroup's 256 leaf rows stay in LDS and are reduced there; trees of at
@@ -27,6 +32,7 @@
 //    256-leaf tile for the node kernel.  No leaf layer is kept.
 #include <hip/hip_runtime.h>
 
+#include <stddef.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -452,6 +458,158 @@ __global__ __launch_bounds__(kNodeBlock) void merkle_layer_kernel(const uint8_t*
     }
 }
 
+// c ? a : b by value, word by word.  (?: on two uint4 lvalues selects between
+// their addresses, which puts a local one into scratch.)
+__device__ __forceinline__ uint4 pick(bool c, const uint4 a, const uint4 b) {
+    return make_uint4(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w);
+}
+
+// The tile reduction of the layers and proofs kernels: rows [row0, row0 + rows)
+// of src, filled to 1 << levels with the pad row, reduced to t row 0.  rows <=
+// kTile, levels <= kTileLog2; every thread of the workgroup calls this.
+__device__ __forceinline__ void reduce_rows(Rows& t, const uint4* src, uint64_t row0, uint32_t rows, uint32_t levels,
+                                            const uint4 pad_lo, const uint4 pad_hi) {
+    const uint32_t i = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const uint32_t r = i + k * kNodeBlock;
+        uint4 lo = pad_lo, hi = pad_hi;
+        if (r < rows) {
+            lo = src[(row0 + r) * 2];
+            hi = src[(row0 + r) * 2 + 1];
+        }
+        t.lo[r] = lo;
+        t.hi[r] = hi;
+    }
+    __syncthreads();
+    for (uint32_t L = 0; L < levels; ++L) reduce_level(t, (1u << levels) >> (L + 1));
+}
+
+// One pass of the segmented layer reduction (vx_merkle_device_layers): workgroup
+// b executes tile tiles[b] of the host's plan (vx_merkle_layers.hpp).  The
+// descriptor's address is workgroup-uniform, so it is fetched once per wave
+// with scalar loads.  in: d_hashes in pass 0, the work area later; a tile that
+// is not its layer's last writes a work row that only the next launch reads.
+__global__ __launch_bounds__(kNodeBlock) void merkle_layers_kernel(const uint8_t* in,
+                                                                   const vx_merkle_tile* __restrict__ tiles,
+                                                                   uint4 pad_lo, uint4 pad_hi, uint8_t* work,
+                                                                   uint8_t* __restrict__ roots,
+                                                                   const uint8_t* __restrict__ expected,
+                                                                   uint8_t* __restrict__ matched) {
+    __shared__ Rows t;
+    // (as words: the 16- and 8-bit fields have no scalar load of their own)
+    const uint32_t* d = reinterpret_cast<const uint32_t*>(tiles + blockIdx.x);
+    const uint32_t in_row = d[0], out = d[1], packed = d[2];  // rows | levels << 16 | last << 24
+    const uint32_t d_rows = packed & 0xFFFFu, d_levels = (packed >> 16) & 0xFFu, last = packed >> 24;
+    // (a plan is the host's own, but a clamp costs nothing and keeps the tile inside LDS whatever it holds)
+    const uint32_t rows = d_rows < kTile ? d_rows : kTile;
+    const uint32_t levels = d_levels < (uint32_t)kTileLog2 ? d_levels : (uint32_t)kTileLog2;
+    reduce_rows(t, reinterpret_cast<const uint4*>(in), in_row, rows, levels, pad_lo, pad_hi);
+    if (threadIdx.x == 0) {
+        if (last) {
+            emit_root(Row{t.lo[0], t.hi[0]}, out, roots, expected, matched);
+        } else {
+            uint4* o = reinterpret_cast<uint4*>(work + (size_t)out * 32);
+            o[0] = t.lo[0];
+            o[1] = t.hi[0];
+        }
+    }
+}
+
+static_assert(sizeof(vx_merkle_tile) == 16 && offsetof(vx_merkle_tile, rows) == 8 &&
+                  offsetof(vx_merkle_tile, levels) == 10 && offsetof(vx_merkle_tile, last) == 11,
+              "merkle_layers_kernel reads the descriptor as words");
+static_assert(sizeof(vx_merkle_proof) == 24 && offsetof(vx_merkle_proof, row) == 8 &&
+                  offsetof(vx_merkle_proof, span) == 16 && offsetof(vx_merkle_proof, uncles) == 18,
+              "merkle_proof_span_kernel reads the descriptor as words");
+
+// Hash proofs (vx_merkle_device_proofs).  A descriptor comes off the wire, so
+// both kernels check it before any row of the proof is read.
+__device__ __forceinline__ bool proof_ok(uint32_t span, uint32_t uncles) {
+    return span >= 1 && span <= kTile && (span & (span - 1)) == 0 && uncles <= 64;
+}
+
+// First launch: workgroup b reduces the span of proof b (span rows from row
+// p.row of hashes) to its root in tops row b; a span of 1 is a copy.  A bad
+// descriptor gets the zero row.
+__global__ __launch_bounds__(kNodeBlock) void merkle_proof_span_kernel(const uint8_t* __restrict__ hashes,
+                                                                       const vx_merkle_proof* __restrict__ proofs,
+                                                                       uint8_t* __restrict__ tops) {
+    __shared__ Rows t;
+    // (as words: a copy of the struct, with its byte array, would live in scratch,
+    // and the 16- and 8-bit fields have no scalar load of their own)
+    const uint32_t* d = reinterpret_cast<const uint32_t*>(proofs + blockIdx.x);
+    const uint32_t row = d[2], span = d[4] & 0xFFFFu, uncles = (d[4] >> 16) & 0xFFu;
+    const uint4 zero = make_uint4(0, 0, 0, 0);
+    uint4* o = reinterpret_cast<uint4*>(tops + (size_t)blockIdx.x * 32);
+    if (!proof_ok(span, uncles)) {  // (workgroup-uniform)
+        if (threadIdx.x == 0) {
+            o[0] = zero;
+            o[1] = zero;
+        }
+        return;
+    }
+    const uint32_t levels = 31u - (uint32_t)__builtin_clz(span);
+    reduce_rows(t, reinterpret_cast<const uint4*>(hashes), row, span, levels, zero, zero);
+    if (threadIdx.x == 0) {
+        o[0] = t.lo[0];
+        o[1] = t.hi[0];
+    }
+}
+
+// Second launch: lane g walks proof g's uncles from the span's root in tops
+// row g (the first launch's), leaves the top there and sets the verdict.  The
+// loop bound is the wave's largest uncle count; a lane past its own count
+// loads nothing and keeps its hash (as the leaf kernels treat group counts).
+__global__ __launch_bounds__(kBlock) void merkle_proof_walk_kernel(const uint8_t* __restrict__ hashes,
+                                                                   const vx_merkle_proof* __restrict__ proofs,
+                                                                   uint32_t n, uint8_t* tops,
+                                                                   const uint8_t* __restrict__ expected,
+                                                                   uint8_t* __restrict__ matched) {
+    const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
+    // Lanes past the last proof redo it (in bounds, the wave stays convergent) and store nothing.
+    const vx_merkle_proof* p = proofs + (g < n ? g : n - 1);
+    const uint32_t span = p->span, uncles = p->uncles, row = p->row;
+    const uint64_t pos = p->pos;
+    const bool ok = proof_ok(span, uncles);
+    const uint32_t un = ok && g < n ? uncles : 0;
+    const uint32_t un_wave = __builtin_amdgcn_readfirstlane(wave_max(un));
+    const uint4 zero = make_uint4(0, 0, 0, 0);
+    uint4* top = reinterpret_cast<uint4*>(tops) + (size_t)(g < n ? g : n - 1) * 2;
+    const uint4* uncle = reinterpret_cast<const uint4*>(hashes) + ((uint64_t)row + span) * 2;
+    uint4 c0 = zero, c1 = zero;
+    if (g < n) {
+        c0 = top[0];
+        c1 = top[1];
+    }
+    for (uint32_t k = 0; k < un_wave; ++k) {
+        const bool on = k < un;
+        uint4 u0 = zero, u1 = zero;
+        if (on) {
+            u0 = uncle[2 * k];
+            u1 = uncle[2 * k + 1];
+        }
+        const bool right = (pos >> k) & 1;  // (k < 64)
+        uint4 o0, o1;
+        node_hash(o0, o1, pick(right, u0, c0), pick(right, u1, c1), pick(right, c0, u0), pick(right, c1, u1));
+        c0 = pick(on, o0, c0);
+        c1 = pick(on, o1, c1);
+    }
+    if (g >= n) return;
+    if (!ok) {
+        top[0] = zero;
+        top[1] = zero;
+        matched[g] = 0;
+        return;
+    }
+    top[0] = c0;
+    top[1] = c1;
+    const uint32_t* x = reinterpret_cast<const uint32_t*>(expected + (size_t)p->expected * 32);  // 4-byte aligned
+    const bool same = (x[0] == c0.x) & (x[1] == c0.y) & (x[2] == c0.z) & (x[3] == c0.w) & (x[4] == c1.x) &
+                      (x[5] == c1.y) & (x[6] == c1.z) & (x[7] == c1.w);
+    matched[g] = same ? 1 : 0;
+}
+
 hipError_t launch_nodes(uint32_t n, uint32_t log2_width, const uint8_t* leaves, const uint8_t* log2w, uint8_t* roots,
                         const uint8_t* expected, uint8_t* matched, hipStream_t stream) {
     if (!roots && !(expected && matched)) return hipSuccess;
@@ -545,6 +703,33 @@ hipError_t launch_merkle_root(const uint8_t* layer, uint32_t n, uint8_t* work, u
         done += levels;
     }
     return hipSuccess;
+}
+
+hipError_t launch_merkle_layers(const uint8_t* hashes, const struct vx_merkle_layers_plan& plan,
+                                const vx_merkle_tile* tiles, uint8_t* work, uint8_t* roots, const uint8_t* expected,
+                                uint8_t* matched, const uint8_t (*pads)[32], hipStream_t stream) {
+    uint32_t first = 0;
+    for (uint32_t p = 0; p < plan.passes; ++p) {
+        uint4 pad[2];  // rows are bytes: the words as the device loads them
+        memcpy(pad, pads[p], 32);
+        hipLaunchKernelGGL(merkle_layers_kernel, dim3(plan.pass_tiles[p]), dim3(kNodeBlock), 0, stream,
+                           p == 0 ? hashes : work, tiles + first, pad[0], pad[1], work, roots, expected, matched);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        first += plan.pass_tiles[p];
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_merkle_proofs(const uint8_t* hashes, const vx_merkle_proof* proofs, uint32_t n, uint8_t* tops,
+                                const uint8_t* expected, uint8_t* matched, hipStream_t stream) {
+    hipLaunchKernelGGL(merkle_proof_span_kernel, dim3(n), dim3(kNodeBlock), 0, stream, hashes, proofs, tops);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const uint32_t grid = (uint32_t)(((uint64_t)n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(merkle_proof_walk_kernel, dim3(grid), dim3(kBlock), 0, stream, hashes, proofs, n, tops,
+                       expected, matched);
+    return hipGetLastError();
 }
 
 }  // namespace vx

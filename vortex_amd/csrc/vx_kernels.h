@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vx_hash.h"  // vx_merkle_tile, vx_merkle_layers_plan, vx_merkle_proof
+
 namespace vx {
 
 constexpr int kBlock = 256;  // 4 waves = one wave per SIMD of a CU
@@ -113,6 +115,16 @@ hipError_t launch_merkle_nodes(const uint8_t* leaves, const uint8_t* log2w, uint
 // height + k (one per level to the root); work: 32*n bytes.
 hipError_t launch_merkle_root(const uint8_t* layer, uint32_t n, uint8_t* work, uint8_t* root,
                               const uint8_t (*pads)[32], hipStream_t stream);
+// Many layers in plan.passes launches (vx_merkle_device_layers): tiles is the
+// device copy of the planner's tiles, pads[p] the pad hash of the layers'
+// height + 9p, work plan.work_rows rows.
+hipError_t launch_merkle_layers(const uint8_t* hashes, const struct vx_merkle_layers_plan& plan,
+                                const vx_merkle_tile* tiles, uint8_t* work, uint8_t* roots, const uint8_t* expected,
+                                uint8_t* matched, const uint8_t (*pads)[32], hipStream_t stream);
+// Hash proofs in two launches (vx_merkle_device_proofs): the spans' roots into
+// tops, then the uncle walks, the tops in place and the verdicts.
+hipError_t launch_merkle_proofs(const uint8_t* hashes, const vx_merkle_proof* proofs, uint32_t n, uint8_t* tops,
+                                const uint8_t* expected, uint8_t* matched, hipStream_t stream);
 
 hipError_t launch_synth_fill(uint8_t* base, uint64_t stride, uint32_t len, uint32_t n, uint64_t first,
                              uint64_t seed, uint32_t corrupt_every, hipStream_t stream);

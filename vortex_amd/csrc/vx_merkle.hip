@@ -1,6 +1,8 @@
 // vx_merkle.hip — the BitTorrent v2 merkle entries of vx_hash.h (kernels in
-// sha256_kernels.hip): vx_merkle_device_*, _verify_batch, _verify_files.
+// sha256_kernels.hip): vx_merkle_device_*, _verify_batch, _verify_files,
+// _layers_plan, _verify_layers, _verify_proofs.
 #include "vx_engine_internal.hpp"
+#include "vx_merkle_layers.hpp"
 
 using namespace vxe;
 
@@ -584,6 +586,166 @@ static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint
         }
     }
     return end_files_call(c, fds, bad, t_call, rc);
+}
+
+// ---- `piece layers` and hash proofs in batches ----
+
+int vx_merkle_layers_plan(const uint32_t* counts, uint32_t n_layers, struct vx_merkle_layers_plan* plan,
+                          vx_merkle_tile* tiles, size_t tiles_cap) {
+    if (!plan || (n_layers && !counts)) return fail(VX_EINVAL, "vx_merkle_layers_plan: NULL plan or counts");
+    struct vx_merkle_layers_plan pl;
+    if (vx_merkle::plan_layers(counts, n_layers, &pl, nullptr, 0))
+        return fail(VX_EINVAL, "vx_merkle_layers_plan: a count is 0, or the counts sum to 2^32 rows or more");
+    if (tiles && tiles_cap < pl.n_tiles) return fail(VX_EINVAL, "vx_merkle_layers_plan: tiles_cap < n_tiles");
+    return vx_merkle::plan_layers(counts, n_layers, plan, tiles, tiles_cap);
+}
+
+int vx_merkle_device_layers(const void* d_hashes, const struct vx_merkle_layers_plan* plan,
+                            const vx_merkle_tile* d_tiles, uint32_t height, void* d_work, void* d_roots,
+                            const void* d_expected, void* d_matched, void* stream) {
+    if (!plan) return fail(VX_EINVAL, "vx_merkle_device_layers: NULL plan");
+    if (plan->n_layers == 0) return 0;
+    if (!d_hashes || !d_tiles || (plan->work_rows && !d_work))
+        return fail(VX_EINVAL, "vx_merkle_device_layers: NULL d_hashes, d_tiles or d_work");
+    if ((reinterpret_cast<uintptr_t>(d_hashes) | reinterpret_cast<uintptr_t>(d_work) |
+         reinterpret_cast<uintptr_t>(d_roots)) & 15)
+        return fail(VX_EINVAL, "vx_merkle_device_layers: d_hashes, d_work and d_roots must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_tiles) | reinterpret_cast<uintptr_t>(d_expected)) & 3)
+        return fail(VX_EINVAL, "vx_merkle_device_layers: d_tiles and d_expected must be 4-byte aligned");
+    if (height > 64) return fail(VX_EINVAL, "vx_merkle_device_layers: height > 64");
+    uint64_t tiles = 0;
+    for (uint32_t p = 0; p < 4; ++p) tiles += p < plan->passes ? plan->pass_tiles[p] : 0;
+    if (plan->passes > 4 || tiles != plan->n_tiles)
+        return fail(VX_EINVAL, "vx_merkle_device_layers: not a plan of vx_merkle_layers_plan (passes, pass_tiles)");
+    uint8_t pads[4][32];  // pad(height + 9p), one per pass
+    for (int p = 0; p < 4; ++p) vx_merkle_pad_hash(height + 9 * p, pads[p]);
+    const bool verdict = d_expected && d_matched;
+    hipError_t e = vx::launch_merkle_layers(static_cast<const uint8_t*>(d_hashes), *plan, d_tiles,
+                                            static_cast<uint8_t*>(d_work), static_cast<uint8_t*>(d_roots),
+                                            verdict ? static_cast<const uint8_t*>(d_expected) : nullptr,
+                                            verdict ? static_cast<uint8_t*>(d_matched) : nullptr, pads,
+                                            static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "merkle layers kernel launch");
+    return 0;
+}
+
+int vx_merkle_device_proofs(const void* d_hashes, const vx_merkle_proof* d_proofs, uint32_t n, void* d_tops,
+                            const void* d_expected, void* d_matched, void* stream) {
+    if (n == 0) return 0;
+    if (!d_hashes || !d_proofs || !d_tops || !d_expected || !d_matched)
+        return fail(VX_EINVAL, "vx_merkle_device_proofs: NULL argument");
+    if ((reinterpret_cast<uintptr_t>(d_hashes) | reinterpret_cast<uintptr_t>(d_tops)) & 15)
+        return fail(VX_EINVAL, "vx_merkle_device_proofs: d_hashes and d_tops must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_proofs) & 7) || (reinterpret_cast<uintptr_t>(d_expected) & 3))
+        return fail(VX_EINVAL, "vx_merkle_device_proofs: d_proofs must be 8-byte and d_expected 4-byte aligned");
+    hipError_t e = vx::launch_merkle_proofs(static_cast<const uint8_t*>(d_hashes), d_proofs, n,
+                                            static_cast<uint8_t*>(d_tops), static_cast<const uint8_t*>(d_expected),
+                                            static_cast<uint8_t*>(d_matched), static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "merkle proof kernel launch");
+    return 0;
+}
+
+namespace {
+// The stream and the one device block of a vx_merkle_verify_layers / _proofs
+// call: made per call, gone when it returns (once per torrent or per batch of
+// messages; the batch slots and their streams stay with the pieces).
+struct CallBufs {
+    hipStream_t stream = nullptr;
+    uint8_t* d = nullptr;
+    ~CallBufs() {
+        if (stream) {
+            (void)hipStreamSynchronize(stream);  // error path: no copy may still use the caller's memory
+            (void)hipStreamDestroy(stream);
+        }
+        if (d) (void)hipFree(d);
+    }
+    int make(const vx_ctx* c, uint64_t bytes, const char* who) {
+        int rc = set_device(c);
+        if (rc) return rc;
+        if (hipMalloc(&d, bytes) != hipSuccess) {
+            d = nullptr;
+            return fail(VX_ENOMEM, std::string(who) + ": buffer allocation failed");
+        }
+        VX_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        return 0;
+    }
+};
+}  // namespace
+
+int vx_merkle_verify_layers(vx_ctx* c, const uint8_t* hashes, const uint32_t* counts, uint32_t n_layers,
+                            uint32_t height, const uint8_t* expected, uint8_t* matched_out, uint8_t* roots_out) {
+    const char* who = "vx_merkle_verify_layers";
+    if (!c) return fail(VX_EINVAL, std::string(who) + ": NULL context");
+    if (n_layers && (!hashes || !counts || !expected || !matched_out))
+        return fail(VX_EINVAL, std::string(who) + ": NULL hashes/counts/expected/matched_out");
+    if (height > 64) return fail(VX_EINVAL, std::string(who) + ": height > 64");
+    if (n_layers == 0) return 0;
+    struct vx_merkle_layers_plan plan;
+    if (vx_merkle::plan_layers(counts, n_layers, &plan, nullptr, 0))
+        return fail(VX_EINVAL, std::string(who) + ": a count is 0, or the counts sum to 2^32 rows or more");
+    if (c->sticky) return c->sticky;
+    std::vector<vx_merkle_tile> tiles(plan.n_tiles);
+    (void)vx_merkle::plan_layers(counts, n_layers, &plan, tiles.data(), tiles.size());
+    // hashes | work | roots | expected | tiles | verdicts: every part but the last a multiple of 16 bytes
+    const uint64_t o_work = plan.rows * 32, o_roots = o_work + plan.work_rows * 32;
+    const uint64_t o_exp = o_roots + (uint64_t)n_layers * 32, o_tiles = o_exp + (uint64_t)n_layers * 32;
+    const uint64_t o_match = o_tiles + (uint64_t)plan.n_tiles * sizeof(vx_merkle_tile);
+    CallBufs b;
+    int rc = b.make(c, o_match + n_layers, who);
+    if (rc) return rc;
+    VX_HIP(hipMemcpyAsync(b.d, hashes, plan.rows * 32, hipMemcpyHostToDevice, b.stream));
+    VX_HIP(hipMemcpyAsync(b.d + o_exp, expected, (size_t)n_layers * 32, hipMemcpyHostToDevice, b.stream));
+    VX_HIP(hipMemcpyAsync(b.d + o_tiles, tiles.data(), tiles.size() * sizeof(vx_merkle_tile), hipMemcpyHostToDevice,
+                          b.stream));
+    rc = vx_merkle_device_layers(b.d, &plan, reinterpret_cast<const vx_merkle_tile*>(b.d + o_tiles), height,
+                                 b.d + o_work, b.d + o_roots, b.d + o_exp, b.d + o_match, b.stream);
+    if (rc) return rc;
+    if (roots_out) VX_HIP(hipMemcpyAsync(roots_out, b.d + o_roots, (size_t)n_layers * 32, hipMemcpyDeviceToHost, b.stream));
+    VX_HIP(hipMemcpyAsync(matched_out, b.d + o_match, n_layers, hipMemcpyDeviceToHost, b.stream));
+    VX_HIP(hipStreamSynchronize(b.stream));
+    return 0;
+}
+
+int vx_merkle_verify_proofs(vx_ctx* c, const uint8_t* hashes, uint64_t n_rows, const vx_merkle_proof* proofs,
+                            uint32_t n, const uint8_t* expected, uint32_t n_expected, uint8_t* matched_out,
+                            uint8_t* tops_out) {
+    const char* who = "vx_merkle_verify_proofs";
+    if (!c) return fail(VX_EINVAL, std::string(who) + ": NULL context");
+    if (n && (!hashes || !proofs || !expected || !matched_out))
+        return fail(VX_EINVAL, std::string(who) + ": NULL hashes/proofs/expected/matched_out");
+    for (uint32_t i = 0; i < n; ++i) {  // wire-derived numbers: checked before anything is copied
+        const vx_merkle_proof& p = proofs[i];
+        const char* bad = nullptr;
+        if (p.span == 0 || p.span > VX_MERKLE_TILE_ROWS || (p.span & (p.span - 1)))
+            bad = "span is not a power of two in 1..512";
+        else if (p.uncles > 64)
+            bad = "uncles > 64";
+        else if ((uint64_t)p.row + p.span + p.uncles > n_rows)
+            bad = "row + span + uncles > n_rows";
+        else if (p.expected >= n_expected)
+            bad = "expected >= n_expected";
+        if (bad) return fail(VX_EINVAL, std::string(who) + ": proof " + std::to_string(i) + ": " + bad);
+    }
+    if (n == 0) return 0;
+    if (c->sticky) return c->sticky;
+    // hashes | tops | expected | proofs | verdicts: every part but the last a multiple of 8 bytes
+    const uint64_t o_tops = n_rows * 32, o_exp = o_tops + (uint64_t)n * 32;
+    const uint64_t o_proofs = o_exp + (uint64_t)n_expected * 32;
+    const uint64_t o_match = o_proofs + (uint64_t)n * sizeof(vx_merkle_proof);
+    CallBufs b;
+    int rc = b.make(c, o_match + n, who);
+    if (rc) return rc;
+    VX_HIP(hipMemcpyAsync(b.d, hashes, n_rows * 32, hipMemcpyHostToDevice, b.stream));
+    VX_HIP(hipMemcpyAsync(b.d + o_exp, expected, (size_t)n_expected * 32, hipMemcpyHostToDevice, b.stream));
+    VX_HIP(hipMemcpyAsync(b.d + o_proofs, proofs, (size_t)n * sizeof(vx_merkle_proof), hipMemcpyHostToDevice,
+                          b.stream));
+    rc = vx_merkle_device_proofs(b.d, reinterpret_cast<const vx_merkle_proof*>(b.d + o_proofs), n, b.d + o_tops,
+                                 b.d + o_exp, b.d + o_match, b.stream);
+    if (rc) return rc;
+    if (tops_out) VX_HIP(hipMemcpyAsync(tops_out, b.d + o_tops, (size_t)n * 32, hipMemcpyDeviceToHost, b.stream));
+    VX_HIP(hipMemcpyAsync(matched_out, b.d + o_match, n, hipMemcpyDeviceToHost, b.stream));
+    VX_HIP(hipStreamSynchronize(b.stream));
+    return 0;
 }
 
 int64_t vx_merkle_verify_files_range(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,

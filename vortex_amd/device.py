@@ -442,6 +442,140 @@ def merkle_root(layer: torch.Tensor, height: int = 0, stream: Optional[torch.cud
     return root
 
 
+def _upload(buf, dev, stream: Optional[torch.cuda.Stream]) -> torch.Tensor:
+    """A host ctypes array as a uint8 device tensor, copied on the stream that
+    will read it.  Through pinned memory and without blocking: a copy from
+    pageable memory would wait for everything already on the stream, and the
+    host's planning of one call could not overlap the kernels of the last
+    (0.76 against 0.67 ms per call on one layer of 4 M hashes).
+    torch keeps the pinned block alive until the copy has run."""
+    host = torch.frombuffer(buf, dtype=torch.uint8).pin_memory()
+    if stream is None:
+        return host.to(dev, non_blocking=True)
+    with torch.cuda.stream(stream):
+        t = host.to(dev, non_blocking=True)
+    return t
+
+
+def merkle_layers(hashes: torch.Tensor, counts, height: int, expected: Optional[torch.Tensor] = None,
+                  roots: Optional[torch.Tensor] = None, matched: Optional[torch.Tensor] = None,
+                  stream: Optional[torch.cuda.Stream] = None):
+    """Roots of many layers in one call (vx_merkle_device_layers): `hashes`
+    ([sum(counts),32] uint8) holds the layers back to back, layer f counts[f]
+    >= 1 hashes, all `height` levels above the leaves (a torrent's `piece
+    layers`: merkle.layer_counts, height = log2(piece_length / 16 KiB)).
+    counts is a host sequence: the host plans the tiles, the device runs one
+    launch per pass (at most 4) whatever the number of layers.  With
+    `expected` ([n,32], the files' `pieces root`) matched[f] = (root ==
+    expected[f]).  roots: None allocates them, except with `expected` given,
+    where None asks for verdicts only.  Returns (roots or None, matched or
+    None).  Enqueue-only but for the upload of the tiles."""
+    import ctypes
+
+    from . import _lib
+
+    _req(hashes, "hashes")
+    dev = hashes.device
+    n = len(counts)
+    host_counts = [int(c) for c in counts]
+    if any(not 0 <= c < 1 << 32 for c in host_counts):
+        raise ValueError("merkle_layers: a count is outside 0..2^32-1")
+    carr = (ctypes.c_uint32 * max(n, 1))(*host_counts)
+    if not 0 <= height <= 64:
+        raise ValueError("merkle_layers: height must be 0..64")
+    plan = _lib.vx_merkle_layers_plan()
+    check(lib().vx_merkle_layers_plan(carr, n, ctypes.byref(plan), None, 0), "vx_merkle_layers_plan")
+    if hashes.numel() != 32 * plan.rows:
+        raise ValueError(f"hashes must hold sum(counts) = {plan.rows} rows of 32 bytes")
+    if roots is not None:
+        _req(roots, "roots")
+        if roots.numel() < 32 * n or roots.device != dev:
+            raise ValueError("roots must hold n*32 bytes on the hashes' device")
+    elif expected is None:
+        roots = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    if expected is not None:
+        _req(expected, "expected")
+        if expected.numel() < 32 * n or expected.device != dev:
+            raise ValueError("expected must hold n*32 bytes on the hashes' device")
+        if matched is None:
+            matched = torch.empty((n,), dtype=torch.uint8, device=dev)
+        else:
+            _req(matched, "matched")
+            if matched.numel() < n or matched.device != dev:
+                raise ValueError("matched must hold n bytes on the hashes' device")
+    else:
+        matched = None
+    if n == 0:
+        return roots, matched
+    tiles = (_lib.vx_merkle_tile * plan.n_tiles)()
+    check(lib().vx_merkle_layers_plan(carr, n, ctypes.byref(plan), tiles, plan.n_tiles), "vx_merkle_layers_plan")
+    d_tiles = _upload(tiles, dev, stream)
+    work = torch.empty((max(int(plan.work_rows), 1), 32), dtype=torch.uint8, device=dev)
+    if stream is not None:  # the scratch and the tiles outlive this call on the stream that uses them
+        work.record_stream(stream)
+        d_tiles.record_stream(stream)
+    rc = lib().vx_merkle_device_layers(hashes.data_ptr(), ctypes.byref(plan), d_tiles.data_ptr(), height,
+                                       work.data_ptr(), roots.data_ptr() if roots is not None else None,
+                                       expected.data_ptr() if expected is not None else None,
+                                       matched.data_ptr() if matched is not None else None, _stream_ptr(stream, dev))
+    check(rc, "vx_merkle_device_layers")
+    return roots, matched
+
+
+def check_proofs(proofs, n_rows: int, n_expected: int):
+    """A host sequence of proofs, each (pos, row, expected, span, uncles) or a
+    ``vx_merkle_proof``, as a ctypes array after the checks of
+    vx_merkle_verify_proofs: span a power of two of at most 512, uncles <= 64,
+    row + span + uncles <= n_rows, expected < n_expected.  ValueError names the
+    first bad index."""
+    from . import _lib
+
+    arr = _lib.proof_array(proofs)
+    for i in range(len(proofs)):
+        span, uncles = arr[i].span, arr[i].uncles
+        if not (1 <= span <= _lib.VX_MERKLE_TILE_ROWS and span & (span - 1) == 0):
+            raise ValueError(f"proof {i}: span is not a power of two in 1..512")
+        if uncles > 64:
+            raise ValueError(f"proof {i}: uncles > 64")
+        if arr[i].row + span + uncles > n_rows:
+            raise ValueError(f"proof {i}: row + span + uncles > n_rows")
+        if arr[i].expected >= n_expected:
+            raise ValueError(f"proof {i}: expected >= n_expected")
+    return arr
+
+
+def merkle_proofs(hashes: torch.Tensor, proofs, expected: torch.Tensor,
+                  stream: Optional[torch.cuda.Stream] = None):
+    """Verify hash proofs in one call of two launches
+    (vx_merkle_device_proofs).  `hashes` ([R,32] uint8) holds every proof's
+    rows as they came off the wire, its span then its uncles; `proofs` is a
+    host sequence of (pos, row, expected, span, uncles) (or
+    ``vx_merkle_proof``), checked as by :func:`check_proofs`; `expected`
+    ([E,32]) the trusted rows.  Returns (tops [n,32], matched [n]): tops[i] is
+    where proof i's walk ended, matched[i] = (tops[i] == expected[proofs[i].expected]).
+    Enqueue-only but for the upload of the proofs."""
+    _req(hashes, "hashes")
+    _req(expected, "expected")
+    dev = hashes.device
+    if expected.device != dev:
+        raise ValueError(f"expected is on {expected.device}, hashes on {dev}")
+    if hashes.numel() % 32 or expected.numel() % 32:
+        raise ValueError("hashes and expected must hold whole 32-byte rows")
+    n = len(proofs)
+    arr = check_proofs(proofs, hashes.numel() // 32, expected.numel() // 32)
+    tops = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    matched = torch.empty((n,), dtype=torch.uint8, device=dev)
+    if n == 0:
+        return tops, matched
+    d_proofs = _upload(arr, dev, stream)
+    if stream is not None:
+        d_proofs.record_stream(stream)
+    rc = lib().vx_merkle_device_proofs(hashes.data_ptr(), d_proofs.data_ptr(), n, tops.data_ptr(),
+                                       expected.data_ptr(), matched.data_ptr(), _stream_ptr(stream, dev))
+    check(rc, "vx_merkle_device_proofs")
+    return tops, matched
+
+
 def ragged_plan(lens_host) -> tuple[int, int]:
     """(longest piece, total bytes) of a ragged batch: the `plan` argument of
     :func:`sha1_ragged`."""

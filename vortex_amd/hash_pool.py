@@ -36,8 +36,8 @@ import os
 from dataclasses import dataclass
 from typing import Any, Optional, Sequence
 
-from . import _lib
-from ._lib import CONFIG_OPTIONS, VxError, check, lib, vx_completion, vx_config, vx_stats
+from . import _lib, merkle
+from ._lib import CONFIG_OPTIONS, VxError, check, lib, proof_array, vx_completion, vx_config, vx_stats
 
 
 @dataclass
@@ -415,6 +415,50 @@ class HashPool:
               "vx_merkle_verify_batch", self.lib)
         raw = roots.raw
         return [bool(b) for b in matched.raw[:n]], [raw[32 * i: 32 * i + 32] for i in range(n)]
+
+    def verify_piece_layers(self, layers: Sequence[bytes], roots: Sequence[bytes], piece_length: int) -> list[bool]:
+        """Check a v2 torrent's `piece layers` against the files' `pieces root`
+        (vx_merkle_verify_layers): layers[f] is one file's string of 32-byte
+        piece hashes, roots[f] that file's `pieces root`; every layer is padded
+        to a power of two with the pad hash of a piece and reduced on the
+        device, all files in one call.  Only after this may the layers serve as
+        the `expected` of the piece calls.  Works while async pieces are
+        pending and leaves stats() alone.  Returns one bool per file."""
+        n = len(layers)
+        if len(roots) != n:
+            raise ValueError("roots must have one `pieces root` per layer")
+        if any(len(x) == 0 or len(x) % 32 for x in layers) or any(len(r) != 32 for r in roots):
+            raise ValueError("a layer is a non-empty string of 32-byte hashes, a root 32 bytes")
+        height = merkle.log2_width(piece_length)
+        blob = b"".join(bytes(x) for x in layers)
+        hashes = ctypes.create_string_buffer(blob, max(1, len(blob)))
+        counts = (ctypes.c_uint32 * max(n, 1))(*[len(x) // 32 for x in layers])
+        exp = ctypes.create_string_buffer(b"".join(bytes(r) for r in roots), 32 * max(n, 1))
+        out = ctypes.create_string_buffer(max(n, 1))
+        check(self.lib.vx_merkle_verify_layers(self._h, hashes, counts, n, height, exp, out, None),
+              "vx_merkle_verify_layers", self.lib)
+        return [bool(b) for b in out.raw[:n]]
+
+    def verify_hash_proofs(self, hashes: bytes, proofs: Sequence, expected: Sequence[bytes]) -> list[bool]:
+        """Verify BEP 52 `hashes` messages in one call
+        (vx_merkle_verify_proofs): `hashes` holds every proof's rows as they
+        came off the wire (its span, then its uncles), proofs[i] =
+        (pos, row, expected, span, uncles) says where proof i's rows start,
+        which span of its layer it is and which of the trusted rows in
+        `expected` its walk must reach.  The engine checks every number first
+        (VxError VX_EINVAL names the first bad proof).  Works while async
+        pieces are pending and leaves stats() alone.  Returns one bool per
+        proof."""
+        n = len(proofs)
+        if len(hashes) % 32 or any(len(e) != 32 for e in expected):
+            raise ValueError("hashes and expected hold whole 32-byte rows")
+        arr = proof_array(proofs)
+        buf = ctypes.create_string_buffer(bytes(hashes), max(1, len(hashes)))
+        exp = ctypes.create_string_buffer(b"".join(bytes(e) for e in expected), 32 * max(len(expected), 1))
+        out = ctypes.create_string_buffer(max(n, 1))
+        check(self.lib.vx_merkle_verify_proofs(self._h, buf, len(hashes) // 32, arr, n, exp, len(expected), out,
+                                               None), "vx_merkle_verify_proofs", self.lib)
+        return [bool(b) for b in out.raw[:n]]
 
     def verify_merkle_files(self, paths: Sequence[str], file_lengths: Sequence[int], piece_length: int,
                             expected: bytes, io_threads: int = 0, first: int = 0,

@@ -75,3 +75,84 @@ def pad_hash(height: int) -> bytes:
     for _ in range(height):
         h = hashlib.sha256(h + h).digest()
     return h
+
+
+def _rows(hashes) -> list[bytes]:
+    """A layer as a list of 32-byte rows: bytes-like (n * 32) or a sequence of rows."""
+    if isinstance(hashes, (bytes, bytearray, memoryview)):
+        b = bytes(hashes)
+        if len(b) % 32:
+            raise ValueError("a layer holds whole 32-byte hashes")
+        return [b[k:k + 32] for k in range(0, len(b), 32)]
+    rows = [bytes(r) for r in hashes]
+    if any(len(r) != 32 for r in rows):
+        raise ValueError("a layer holds whole 32-byte hashes")
+    return rows
+
+
+def layer_counts(file_lengths, piece_length: int) -> tuple[list[int], list[int]]:
+    """(counts, file_index) of a torrent's `piece layers`: one layer per file
+    longer than piece_length, ceil(length / piece_length) hashes each, in the
+    order given.  A shorter file has no layer: its one piece's root is its
+    `pieces root` itself.  counts is what ``device.merkle_layers`` takes."""
+    log2_width(piece_length)
+    counts: list[int] = []
+    file_index: list[int] = []
+    for f, length in enumerate(file_lengths):
+        if int(length) > piece_length:
+            counts.append((int(length) + piece_length - 1) // piece_length)
+            file_index.append(f)
+    return counts, file_index
+
+
+class _Tree:
+    """The BEP 52 tree over a layer standing `height` levels above the leaves:
+    node (j, i) is row i of the layer at level 0, the pad hash of its height
+    where its whole subtree lies past the layer, and SHA-256(left || right)
+    otherwise."""
+
+    def __init__(self, rows: list[bytes], height: int):
+        self.levels = [rows]
+        self.height = height
+
+    def node(self, j: int, i: int) -> bytes:
+        n = len(self.levels[0])
+        if (i << j) >= n:
+            return pad_hash(self.height + j)
+        while len(self.levels) <= j:
+            below = len(self.levels) - 1
+            count = (n + (2 << below) - 1) >> (below + 1)
+            self.levels.append([hashlib.sha256(self.node(below, 2 * k) + self.node(below, 2 * k + 1)).digest()
+                                for k in range(count)])
+        return self.levels[j][i]
+
+
+def layer_root(hashes, height: int = 0) -> bytes:
+    """Root of a layer of n >= 1 hashes standing `height` levels above the
+    leaves: padded to the next power of two with pad_hash(height), then reduced
+    pairwise (how a `piece layers` string is checked against `pieces root`;
+    vx_merkle_device_root and vx_merkle_device_layers compute the same)."""
+    rows = _rows(hashes)
+    if not rows:
+        raise ValueError("a layer holds at least one hash")
+    return _Tree(rows, height).node((len(rows) - 1).bit_length(), 0)
+
+
+def make_proof(layer, height: int, pos: int, span: int, uncles: int) -> bytes:
+    """The rows a seeder sends in a `hashes` message for span number `pos` of
+    `span` hashes (a power of two) of `layer`: the span's rows
+    [pos * span, (pos + 1) * span), then `uncles` uncle hashes, the sibling at
+    each step from the span's root upwards.  The layer is padded with
+    pad_hash(height), and the levels above with their own pad hashes, as far
+    as the proof reaches.  (span + uncles) * 32 bytes, the layout of
+    ``vx_merkle_proof``: with uncles = log2(padded layer / span) the walk ends at
+    the layer's root, with fewer at an ancestor."""
+    if span < 1 or span & (span - 1):
+        raise ValueError("span must be a power of two")
+    if pos < 0 or uncles < 0:
+        raise ValueError("pos and uncles must be >= 0")
+    tree = _Tree(_rows(layer), height)
+    out = [tree.node(0, pos * span + k) for k in range(span)]
+    base = span.bit_length() - 1
+    out += [tree.node(base + k, (pos >> k) ^ 1) for k in range(uncles)]
+    return b"".join(out)
