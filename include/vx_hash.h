@@ -637,6 +637,72 @@ int64_t vx_merkle_verify_files_range(vx_ctx* ctx, const char* const* paths, cons
                                      size_t nfiles, uint32_t piece_length, const uint8_t* expected, size_t n_pieces,
                                      size_t first, size_t count, uint8_t* matched_out, uint32_t io_threads);
 
+/* ---- Hybrid (v1 + v2) torrents, BEP 52 "upgrade path" -------------------
+ * One set of files carries a v1 `pieces` table (SHA-1) and v2 `piece layers` /
+ * `pieces root` rows (SHA-256 merkle roots).  Every file but the last is
+ * padded to a piece boundary with a BEP 47 pad file (attr = p, all zeros), so
+ * every file starts its own pieces in v1 too: v1 piece i is v2 piece i (the
+ * numbering of vx_merkle_verify_files), and the v1 piece that ends a file is
+ * its data_len bytes followed by pad_len = piece_length - data_len zeros.  The
+ * torrent's last piece (the last piece of the last non-empty file) has no pad.
+ * Clients do not write pad files; these entries hash the zeros without reading
+ * them from anywhere, and every data byte feeds both hashes from one copy.
+ * A verdict byte has bit 0 set when the SHA-1 matches and bit 1 set when the
+ * merkle root matches; 3 is a good piece, and 1 or 2 on bytes that were read
+ * means the two tables disagree (BEP 52: reject the torrent).
+ *
+ * Device-resident batch: replaces vx_sha1_device_ragged over pieces with their
+ * pads materialised, followed by vx_merkle_device_pieces over the same buffer.
+ * Piece i is d_lens[i] bytes at d_base + d_offsets[i] (16-byte aligned) followed
+ * by d_pads[i] implied zeros; d_pads[i] is 0 or (VX_MERKLE_BLOCK << log2_width)
+ * - d_lens[i].  d_log2w, log2_width, d_roots and d_exp_roots as for
+ * vx_merkle_device_pieces; d_sha1 (may be NULL) gets n * 20 bytes, d_exp_sha1
+ * is n * 20 bytes.  With both expected tables NULL only digests and roots are
+ * returned and d_matched is not written; with one NULL its bit stays clear.
+ * d_work (16-byte aligned): W + 54 * n bytes, where W = 0 for log2_width <= 8
+ * and the (n << (log2_width - 8)) * 32 + n bytes of vx_merkle_device_pieces
+ * rounded up to 16 above (the chunk tables, the SHA-1 states and the two
+ * verdict columns follow the merkle work).  Launches, on the caller's stream:
+ * a table kernel, the chunked SHA-1 kernel over each piece's whole 64-byte
+ * data blocks (a padded piece's state is kept), the zero-tail kernel over the
+ * padded pieces, the merkle piece path, and a kernel that joins the verdicts.
+ * The device-resident metadata is not checked here;
+ * vortex_amd.device.hybrid_pieces checks it.  Enqueue-only; n == 0 launches
+ * nothing. */
+int vx_hybrid_device_pieces(const void* d_base, const uint64_t* d_offsets, const uint32_t* d_lens,
+                            const uint32_t* d_pads, const uint8_t* d_log2w, uint32_t n, uint32_t log2_width,
+                            void* d_work, void* d_sha1, void* d_roots, const void* d_exp_sha1,
+                            const void* d_exp_roots, void* d_matched, void* stream);
+/* Re-verify a hybrid torrent's files from disk in one pass: replaces
+ * vx_verify_files over files plus materialised pad files followed by
+ * vx_merkle_verify_files over the files.  paths / file_lengths list the real
+ * files only, in torrent order with the pad files left out; pad files are
+ * implied, never opened and never read.  exp_sha1 is the v1 `pieces` table
+ * (n_pieces * 20 bytes), exp_roots what vx_merkle_verify_files takes
+ * (n_pieces * 32 bytes), n_pieces the count of vx_merkle_verify_files.
+ * matched_out[i] holds the two verdict bits; a missing, short or unreadable
+ * file gives 0 for exactly the pieces that lack bytes (counted in io_errors).
+ * Returns the number of pieces whose value is not 3, or a negative code.
+ * Every byte is read once and copied to the device once: the files are
+ * streamed in chunk rounds (chunk k of every piece of a window, as
+ * vx_verify_files), each round's bytes feeding the chunked SHA-1 kernel and the
+ * merkle block kernel.  piece_length is a power of two from VX_MERKLE_BLOCK to
+ * 2 GiB and is not bounded by max_piece_len.  io_threads 0 = a default.
+ * VX_EBUSY while async pieces are pending.  Counts into vx_get_stats
+ * (pieces_mismatched once per piece that read well and is not 3) and fills
+ * vx_last_verify (chunk_bytes = the chunk length); vx_last_verify_rounds
+ * returns 0. */
+int64_t vx_hybrid_verify_files(vx_ctx* ctx, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                               uint32_t piece_length, const uint8_t* exp_sha1, const uint8_t* exp_roots,
+                               size_t n_pieces, uint8_t* matched_out, uint32_t io_threads);
+/* Pieces [first, first + count) only, reading only their bytes: replaces the
+ * pair vx_verify_files_range / vx_merkle_verify_files_range.  The expected
+ * tables are whole, matched_out has count entries. */
+int64_t vx_hybrid_verify_files_range(vx_ctx* ctx, const char* const* paths, const uint64_t* file_lengths,
+                                     size_t nfiles, uint32_t piece_length, const uint8_t* exp_sha1,
+                                     const uint8_t* exp_roots, size_t n_pieces, size_t first, size_t count,
+                                     uint8_t* matched_out, uint32_t io_threads);
+
 /* ---- v2 metadata: `piece layers` and hash proofs in batches -------------
  * Every entry above takes its expected rows on trust.  BEP 52 says how a
  * client earns that trust: a file's `piece layers` string must reduce to the

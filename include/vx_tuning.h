@@ -48,6 +48,23 @@ int vx_tuning_zero_copy_plan(uint32_t n, uint64_t total_len);
  * Enqueue-only on `stream` (a hipStream_t or NULL). */
 int vx_tuning_zero_copy_kernel(const uint64_t* d_srcs, const uint32_t* d_lens, uint32_t n, void* d_digests,
                                const void* d_expected, void* d_matched, int loader, void* stream);
+/* The zero-tail kernel on its own (tools/hybrid_tail_bench.py):
+ * lane j finishes a piece of d_lens[j] data bytes followed by d_pads[j] zeros,
+ * d_lens[j] + d_pads[j] == piece_length (a multiple of 64), from
+ * d_states[5j..] (the state after its d_lens[j] >> 6 whole data blocks)
+ * through the d_lens[j] & 63 tail bytes at d_base + d_tail_offs[j]; d_digests
+ * n x 20 B.  Enqueue-only on `stream`. */
+int vx_tuning_zero_tail_kernel(const void* d_base, const uint64_t* d_tail_offs, const uint32_t* d_lens,
+                               const uint32_t* d_pads, uint32_t n, uint64_t piece_length, const uint32_t* d_states,
+                               void* d_digests, void* stream);
+/* The chunked SHA-1 kernel on its own (the same tool): lane j
+ * hashes d_lens[j] bytes at d_base + d_offsets[j] (16-byte aligned) as bytes
+ * [d_poffs[j], +d_lens[j]) of piece d_pids[j], d_tlens[j] bytes in all, from /
+ * to d_states[5 * pid..]; a chunk that ends its piece writes d_digests row
+ * pid, any other (a multiple of 64 bytes) stores the state.  Enqueue-only. */
+int vx_tuning_chunk_kernel(const void* d_base, const uint64_t* d_offsets, const uint32_t* d_lens, uint32_t n,
+                           const uint32_t* d_pids, const uint64_t* d_poffs, const uint64_t* d_tlens,
+                           uint32_t* d_states, void* d_digests, void* stream);
 /* Fault injection for tests: after k more successful piece submits (async or
  * inside a host batch), the next one fails with VX_ENOMEM without latching
  * the context, as a failed pinned-stage allocation does.  k < 0 turns it off. */

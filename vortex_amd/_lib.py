@@ -56,6 +56,7 @@ EXPORTS = (
     "vx_merkle_device_pieces", "vx_merkle_submit", "vx_merkle_poll",
     "vx_merkle_layers_plan", "vx_merkle_device_layers", "vx_merkle_device_proofs", "vx_merkle_verify_layers",
     "vx_merkle_verify_proofs",
+    "vx_hybrid_device_pieces", "vx_hybrid_verify_files", "vx_hybrid_verify_files_range",
 )
 # ... plus include/vx_tuning.h and include/vx_synth.h: libvortex_amd_tuning.so only.
 TUNING_EXPORTS = (
@@ -64,7 +65,7 @@ TUNING_EXPORTS = (
     "vx_tuning_fail_submit_after", "vx_tuning_fail_launch_after", "vx_tuning_verify_copy_stream", "vx_tuning_stage_huge",
     "vx_tuning_split_rules", "vx_tuning_clock_stamp",
     "vx_tuning_wall_clock_khz", "vx_tuning_device_identity", "vx_tuning_split_take_tail",
-    "vx_tuning_last_split",
+    "vx_tuning_last_split", "vx_tuning_zero_tail_kernel", "vx_tuning_chunk_kernel",
 )
 
 
@@ -254,6 +255,11 @@ def _declare(L: ctypes.CDLL, tuning: bool = False) -> None:
         "vx_merkle_device_proofs": ([vp, vp, c.c_uint32, vp, vp, vp, vp], c.c_int),
         "vx_merkle_verify_layers": ([vp, vp, vp, c.c_uint32, c.c_uint32, vp, vp, vp], c.c_int),
         "vx_merkle_verify_proofs": ([vp, vp, c.c_uint64, vp, c.c_uint32, vp, c.c_uint32, vp, vp], c.c_int),
+        "vx_hybrid_device_pieces": ([vp, vp, vp, vp, vp, c.c_uint32, c.c_uint32, vp, vp, vp, vp, vp, vp, vp], c.c_int),
+        "vx_hybrid_verify_files": ([vp, vp, vp, c.c_size_t, c.c_uint32, vp, vp, c.c_size_t, vp, c.c_uint32],
+                                   c.c_int64),
+        "vx_hybrid_verify_files_range": ([vp, vp, vp, c.c_size_t, c.c_uint32, vp, vp, c.c_size_t, c.c_size_t,
+                                          c.c_size_t, vp, c.c_uint32], c.c_int64),
     }
     if tuning:
         sig.update({
@@ -262,6 +268,8 @@ def _declare(L: ctypes.CDLL, tuning: bool = False) -> None:
             "vx_sha1_device_ragged_variant": ([vp, vp, vp, vp, c.c_uint32, vp, vp, vp, vp, c.c_int], c.c_int),
             "vx_tuning_zero_copy_plan": ([c.c_uint32, c.c_uint64], c.c_int),
             "vx_tuning_zero_copy_kernel": ([vp, vp, c.c_uint32, vp, vp, vp, c.c_int, vp], c.c_int),
+            "vx_tuning_zero_tail_kernel": ([vp, vp, vp, vp, c.c_uint32, c.c_uint64, vp, vp, vp], c.c_int),
+            "vx_tuning_chunk_kernel": ([vp, vp, vp, c.c_uint32, vp, vp, vp, vp, vp, vp], c.c_int),
             "vx_tuning_fail_submit_after": ([vp, c.c_int64], None),
             "vx_tuning_fail_launch_after": ([vp, c.c_int64], None),
             "vx_tuning_verify_copy_stream": ([vp, c.c_int], None),

@@ -1,0 +1,387 @@
+// vx_hybrid.hip — the hybrid (BEP 52 "upgrade path", v1 + v2) entries of
+// vx_hash.h: vx_hybrid_device_pieces and vx_hybrid_verify_files / _range
+// (kernels in sha1_kernels.hip, sha1_tail_kernels.hip and sha256_kernels.hip;
+// the rounds in vx_hybrid_rounds.hpp).
+#include "vx_chunk_pipe.hpp"
+#include "vx_hybrid_rounds.hpp"
+
+using namespace vxe;
+
+namespace {
+
+// d_work of vx_hybrid_device_pieces (vx_hash.h): the merkle piece kernel's
+// work, then per piece 24 bytes of uint64 tables, 28 of uint32 and 2 verdicts.
+uint64_t merkle_work_bytes(uint32_t n, uint32_t log2_width) {
+    return log2_width > 8 ? align_up((((uint64_t)n << (log2_width - 8)) * 32) + n, 16) : 0;
+}
+
+// What one files call owns on the device and in pinned memory; gone when it
+// returns (a re-verify is once per torrent; the slots and stages stay with the
+// context).
+struct HybridBufs {
+    uint8_t* d = nullptr;
+    std::vector<uint8_t*> h_tab, d_tab;
+    hipEvent_t chain = nullptr;
+    // The zero-tail kernel runs beside the rounds on a stream of its own (a
+    // 4 MiB pad is a 65,535-block chain that nothing but the verdict waits for):
+    // per slot, `state` after the round's SHA-1 kernel and `tailed` after its tails.
+    hipStream_t tail_stream = nullptr;
+    std::vector<hipEvent_t> state, tailed;
+    ~HybridBufs() {
+        if (tail_stream) {
+            (void)hipStreamSynchronize(tail_stream);
+            (void)hipStreamDestroy(tail_stream);
+        }
+        for (hipEvent_t e : state)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : tailed)
+            if (e) (void)hipEventDestroy(e);
+        if (d) (void)hipFree(d);
+        for (uint8_t* p : h_tab)
+            if (p) (void)hipHostFree(p);
+        for (uint8_t* p : d_tab)
+            if (p) (void)hipFree(p);
+        if (chain) (void)hipEventDestroy(chain);
+    }
+    int make(uint64_t device_bytes, size_t nslots, uint64_t tab_bytes, const std::string& who) {
+        h_tab.assign(nslots, nullptr);
+        d_tab.assign(nslots, nullptr);
+        if (hipMalloc(&d, device_bytes) != hipSuccess) {
+            d = nullptr;
+            return fail(VX_ENOMEM, who + ": buffer allocation failed");
+        }
+        for (size_t k = 0; k < nslots; ++k)
+            if (hipHostMalloc(&h_tab[k], tab_bytes, hipHostMallocDefault) != hipSuccess ||
+                hipMalloc(&d_tab[k], tab_bytes) != hipSuccess)
+                return fail(VX_ENOMEM, who + ": buffer allocation failed");
+        state.assign(nslots, nullptr);
+        tailed.assign(nslots, nullptr);
+        // (lowest priority: the tails yield to the rounds, and HIP keeps a
+        // priority's streams on hardware queues of their own, so no round's
+        // kernel queues behind a long tail)
+        int least = 0, greatest = 0;
+        bool ok = hipEventCreateWithFlags(&chain, hipEventDisableTiming) == hipSuccess &&
+                  hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess &&
+                  hipStreamCreateWithPriority(&tail_stream, hipStreamNonBlocking, least) == hipSuccess;
+        for (size_t k = 0; k < nslots && ok; ++k)
+            ok = hipEventCreateWithFlags(&state[k], hipEventDisableTiming) == hipSuccess &&
+                 hipEventCreateWithFlags(&tailed[k], hipEventDisableTiming) == hipSuccess;
+        if (!ok) return fail(VX_EDEVICE, who + ": stream or event creation failed");
+        return 0;
+    }
+};
+
+int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                          uint32_t piece_length, const uint8_t* exp_sha1, const uint8_t* exp_roots, size_t n_pieces,
+                          size_t first, size_t count, uint8_t* matched_out, uint32_t io_threads) {
+    const std::string who = "vx_hybrid_verify_files";
+    if (!c) return fail(VX_EINVAL, who + ": NULL context");
+    if (!paths || !file_lengths || !exp_sha1 || !exp_roots || !matched_out)
+        return fail(VX_EINVAL, who + ": NULL paths/file_lengths/exp_sha1/exp_roots/matched_out");
+    if (piece_length < VX_MERKLE_BLOCK || (piece_length & (piece_length - 1)))
+        return fail(VX_EINVAL, who + ": piece_length must be a power of two >= 16384");
+    if (n_pieces != vx_merkle::torrent_pieces(file_lengths, nfiles, piece_length))
+        return fail(VX_EINVAL, who + ": n_pieces does not match the files");
+    if (first > n_pieces || count > n_pieces - first) return fail(VX_EINVAL, who + ": piece range outside the torrent");
+    if (count >> 32) return fail(VX_EINVAL, who + ": more than 2^32 pieces in one call");
+    int rc = begin_bulk_call(c, who, /*need_idle=*/true);
+    if (rc) return rc;
+    if (count == 0) return 0;
+    // A round is PCIe-bound when its copy outlasts its chain: at 0.76 us per
+    // block and 50 GiB/s that takes ~640 lanes, so a round holds 1,024 chunks
+    // where the arena allows, and 64 MiB at least.
+    const uint64_t arena = c->slots[0].arena_cap / VX_MERKLE_BLOCK * VX_MERKLE_BLOCK;
+    const uint64_t C = vx_hybrid::chunk_for(piece_length, arena);
+    if (C == 0) return fail(VX_ERANGE, who + ": a slot holds no 16 KiB block");
+    const uint64_t stage = std::min<uint64_t>(arena, std::max<uint64_t>(64ull << 20, 1024 * C));
+    if ((rc = set_device(c))) return rc;
+
+    // What the rounds need at most (a dry run of the planner: no I/O): the
+    // leaf rows of the largest window and the bytes of the largest table.
+    uint64_t rows = 1, tab_bytes = 16;
+    {
+        vx_hybrid::Rounds dry(file_lengths, nfiles, piece_length, n_pieces, first, count, stage, C);
+        vx_hybrid::Round r;
+        while (dry.next(r)) {
+            rows = std::max<uint64_t>(rows, (uint64_t)r.w_n << r.w_log2);
+            tab_bytes = std::max<uint64_t>(tab_bytes, r.l_len.size() * 32 + r.t_len.size() * 20 + r.rows.size() * 8);
+        }
+    }
+    // per piece: state (20) | expected SHA-1 (20) | expected root (32) | v1 verdict | v2 verdict | log2w
+    const uint64_t o_exp1 = count * 20, o_exp2 = align_up(o_exp1 + count * 20, 16), o_v1 = o_exp2 + count * 32;
+    const uint64_t o_v2 = o_v1 + count, o_lw = o_v2 + count, o_leaves = align_up(o_lw + count, 16);
+    // Data copies on the context's copy stream, kernels on the slot streams, as
+    // the v1 chunk rounds: no copy waits behind a kernel.
+    ChunkPipe pipe(c);
+    if (c->verify_copy_stream && (rc = pipe.use_copy_stream())) return rc;
+    HybridBufs hb;
+    if ((rc = hb.make(o_leaves + rows * 32, c->slots.size(), tab_bytes, who))) return rc;
+    uint32_t* d_states = reinterpret_cast<uint32_t*>(hb.d);
+    uint8_t *d_exp1 = hb.d + o_exp1, *d_exp2 = hb.d + o_exp2, *d_v1 = hb.d + o_v1, *d_v2 = hb.d + o_v2;
+    uint8_t *d_lw = hb.d + o_lw, *d_leaves = hb.d + o_leaves;
+
+    const uint64_t t_call = vx_files::Readers::now_ns();
+    c->last_verify = vx_verify_trace{};
+    c->last_rounds.clear();
+    c->verify_t0_ns = t_call;
+    {
+        std::vector<uint8_t> lw(count);
+        vx_merkle::PieceCursor pc(file_lengths, nfiles, piece_length);
+        pc.seek(first);
+        for (size_t i = 0; i < count; ++i, pc.next()) lw[i] = (uint8_t)pc.log2w();
+        if (hipMemcpy(d_exp1, exp_sha1 + 20 * first, count * 20, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_exp2, exp_roots + 32 * first, count * 32, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_lw, lw.data(), count, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemset(d_v1, 0, 2 * count) != hipSuccess ||
+            hipStreamSynchronize(nullptr) != hipSuccess)  // (the slot streams do not wait for the null stream)
+            return fail(VX_EDEVICE, who + ": expected-table upload failed");
+    }
+    std::vector<int> fds(nfiles, -1);
+    for (size_t f = 0; f < nfiles; ++f) fds[f] = open(paths[f], O_RDONLY | O_CLOEXEC);
+    const int nthreads = io_threads ? (int)io_threads : (int)std::max(1u, std::min(16u, usable_cpus()));
+    std::vector<uint8_t> bad(count, 0);
+    std::memset(matched_out, 0, count);
+    const size_t nslots = c->slots.size();
+    const size_t depth = nslots - 1;  // reads run ahead as far as the slots allow (as vx_merkle_verify_files)
+    uint64_t n_rounds = 0, n_bytes = 0, copy_bytes = 0;
+    int64_t n_failed = 0;
+    using clk = std::chrono::steady_clock;
+    auto t_last_enqueue = clk::now();
+    {
+        const std::vector<vx_files::FileSpan> no_spans;
+        const vx_files::DirectIo dio(fds, c->cfg.direct_io != 0);
+        vx_files::Readers rd(nthreads, no_spans, fds, piece_length, bad.data(), first, &dio, true);
+        vx_hybrid::Rounds plan(file_lengths, nfiles, piece_length, n_pieces, first, count, stage, C);
+        std::vector<vx_hybrid::Round> round(nslots);
+        std::vector<std::vector<vx_files::ReadItem>> items(nslots);
+        std::vector<uint64_t> ticket(nslots, 0);
+        std::vector<uint8_t> live(nslots, 0);  // the slot carries an enqueued round
+        bool more = true, have_prev = false;
+        size_t nr = 0;  // next round to read
+        for (size_t ne = 0; !rc; ++ne) {
+            while (more && nr <= ne + depth && !rc) {
+                const size_t si = nr % nslots;
+                Slot& s = c->slots[si];
+                if (live[si]) {  // the round this slot carried: its stage and tables are free again after it
+                    const hipError_t q = nr == ne ? hipEventSynchronize(s.done) : hipEventQuery(s.done);
+                    if (q == hipErrorNotReady) break;  // read-ahead takes only a slot that is free now
+                    if (q != hipSuccess) {
+                        rc = fail(VX_EDEVICE, who + ": wait failed");
+                        break;
+                    }
+                    live[si] = 0;
+                }
+                if (!(more = plan.next(round[si]))) break;
+                if ((rc = ensure_stage(c, s))) break;
+                auto& it = items[si];
+                it.clear();
+                for (const vx_hybrid::Read& r : round[si].reads) {
+                    vx_files::ReadItem x{s.h_stage + r.stage_off, r.piece, 0, r.len};
+                    x.file = (int32_t)r.file;
+                    x.file_off = (int64_t)r.file_off;
+                    it.push_back(x);
+                }
+                ticket[si] = rd.submit(it);
+                ++nr;
+            }
+            if (rc || ne == nr) break;
+            const size_t si = ne % nslots;
+            Slot& s = c->slots[si];
+            const vx_hybrid::Round& r = round[si];
+            rd.wait(ticket[si]);
+            // the round's tables in one copy: the uint64 columns, then the uint32 ones
+            const size_t m = r.l_len.size(), t = r.t_len.size(), e = r.rows.size();
+            uint8_t* h = hb.h_tab[si];
+            size_t at = 0;
+            auto put = [&](const void* src, size_t bytes) {
+                std::memcpy(h + at, src, bytes);
+                const size_t was = at;
+                at += bytes;
+                return was;
+            };
+            const size_t a_loff = put(r.l_off.data(), m * 8), a_lpoff = put(r.l_poff.data(), m * 8);
+            const size_t a_ltlen = put(r.l_tlen.data(), m * 8), a_toff = put(r.t_off.data(), t * 8);
+            const size_t a_llen = put(r.l_len.data(), m * 4), a_lpid = put(r.l_pid.data(), m * 4);
+            const size_t a_tlen = put(r.t_len.data(), t * 4), a_tpad = put(r.t_pad.data(), t * 4);
+            const size_t a_tpid = put(r.t_pid.data(), t * 4), a_rows = put(r.rows.data(), e * 4);
+            const size_t a_lens = put(r.lens.data(), e * 4);
+            uint8_t* d = hb.d_tab[si];
+            auto u64 = [&](size_t o) { return reinterpret_cast<const uint64_t*>(d + o); };
+            auto u32 = [&](size_t o) { return reinterpret_cast<const uint32_t*>(d + o); };
+            hipStream_t cs = pipe.cs ? pipe.cs : s.stream;
+            hipError_t err = hipMemcpyAsync(s.d_arena, s.h_stage, r.bytes, hipMemcpyHostToDevice, cs);
+            if (err == hipSuccess && pipe.cs) err = hipEventRecord(s.copied, cs);
+            if (err == hipSuccess) err = hipMemcpyAsync(d, h, at, hipMemcpyHostToDevice, s.stream);
+            if (err == hipSuccess && pipe.cs) err = hipStreamWaitEvent(s.stream, s.copied, 0);
+            if (err == hipSuccess && have_prev) err = hipStreamWaitEvent(s.stream, hb.chain, 0);
+#ifdef VX_TEST_HOOKS
+            if (err == hipSuccess && c->fail_launch_after >= 0 && c->fail_launch_after-- == 0) {
+                rc = fail(VX_EDEVICE, who + ": injected launch failure (vx_tuning_fail_launch_after)");
+                break;
+            }
+#endif
+            if (err == hipSuccess)
+                err = vx::launch_chunk(s.d_arena, u64(a_loff), u32(a_llen), (uint32_t)m, u32(a_lpid), u64(a_lpoff),
+                                       u64(a_ltlen), d_states, nullptr, d_exp1, d_v1, s.stream);
+            if (err == hipSuccess && t) {  // the tails: after the states, beside everything else
+                err = hipEventRecord(hb.state[si], s.stream);
+                if (err == hipSuccess) err = hipStreamWaitEvent(hb.tail_stream, hb.state[si], 0);
+                if (err == hipSuccess)
+                    err = vx::launch_zero_tail(s.d_arena, u64(a_toff), u32(a_tlen), u32(a_tpad), u32(a_tpid),
+                                               (uint32_t)t, piece_length, d_states, nullptr, d_exp1, d_v1,
+                                               hb.tail_stream);
+                if (err == hipSuccess) err = hipEventRecord(hb.tailed[si], hb.tail_stream);
+            }
+            if (err == hipSuccess)
+                err = vx::launch_merkle_blocks(s.d_arena, u32(a_rows), u32(a_lens), (uint32_t)e, d_leaves, s.stream);
+            if (err == hipSuccess && r.end_window) {
+                const uint64_t k = r.w_first - first;
+                err = vx::launch_merkle_nodes(d_leaves, d_lw + k, r.w_n, r.w_log2, nullptr, d_exp2 + k * 32,
+                                              d_v2 + k, s.stream);
+            }
+            if (err == hipSuccess) err = hipEventRecord(hb.chain, s.stream);
+            // the slot's arena and tables are free again once its tails have read them too
+            if (err == hipSuccess && t) err = hipStreamWaitEvent(s.stream, hb.tailed[si], 0);
+            if (err == hipSuccess) err = hipEventRecord(s.done, s.stream);
+            if (err != hipSuccess) {
+                rc = hip_fail(err, "vx_hybrid_verify_files: enqueue");
+                break;
+            }
+            have_prev = true;
+            live[si] = 1;
+            ++n_rounds;
+            c->stats.chunk_rounds++;
+            n_bytes += r.file_bytes;
+            copy_bytes += r.bytes;
+            t_last_enqueue = clk::now();
+        }
+        rd.wait();  // error path: no read may still target a stage
+        if (pipe.cs && hipStreamSynchronize(pipe.cs) != hipSuccess && !rc)  // ... and no copy may still read one
+            rc = fail(VX_EDEVICE, who + ": a copy failed on the device");
+        for (size_t si = 0; si < nslots; ++si)
+            if (c->slots[si].stream && hipStreamSynchronize(c->slots[si].stream) != hipSuccess && !rc)
+                rc = fail(VX_EDEVICE, who + ": a round failed on the device");
+        if (hipStreamSynchronize(hb.tail_stream) != hipSuccess && !rc)
+            rc = fail(VX_EDEVICE, who + ": a tail kernel failed on the device");
+        std::vector<uint8_t> verdict(2 * count);
+        if (!rc && hipMemcpy(verdict.data(), d_v1, 2 * count, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(VX_EDEVICE, who + ": verdict download failed");
+        vx_verify_trace& vt = c->last_verify;
+        vt.tail_ms = std::chrono::duration<double, std::milli>(clk::now() - t_last_enqueue).count();
+        trace_reads(vt, rd, dio, t_call);
+        vt.rounds = (uint32_t)n_rounds;
+        vt.copy_bytes = copy_bytes;
+        vt.chunk_bytes = C;
+        if (!rc) {
+            uint64_t mism = 0;
+            for (size_t i = 0; i < count; ++i) {
+                const uint8_t v = bad[i] ? 0 : (uint8_t)((verdict[i] ? 1 : 0) | (verdict[count + i] ? 2 : 0));
+                matched_out[i] = v;
+                n_failed += v != 3;
+                mism += v != 3 && !bad[i];  // I/O errors count in io_errors only
+            }
+            c->stats.pieces_completed += count;
+            c->stats.pieces_mismatched += mism;
+            c->stats.bytes_completed += n_bytes;
+            c->stats.batches += n_rounds;
+        }
+    }
+    const int64_t ended = end_files_call(c, fds, bad, t_call, rc);
+    return ended < 0 ? ended : n_failed;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vx_hybrid_device_pieces(const void* d_base, const uint64_t* d_offsets, const uint32_t* d_lens,
+                            const uint32_t* d_pads, const uint8_t* d_log2w, uint32_t n, uint32_t log2_width,
+                            void* d_work, void* d_sha1, void* d_roots, const void* d_exp_sha1,
+                            const void* d_exp_roots, void* d_matched, void* stream) {
+    const char* who = "vx_hybrid_device_pieces";
+    if (log2_width > VX_MERKLE_MAX_LOG2_WIDTH)
+        return fail(VX_EINVAL, std::string(who) + ": log2_width > 17 (piece_length is 16384 << log2_width)");
+    if (!d_base || !d_offsets || !d_lens || !d_pads || !d_work)
+        return fail(VX_EINVAL, std::string(who) + ": NULL d_base, d_offsets, d_lens, d_pads or d_work");
+    if ((d_exp_sha1 || d_exp_roots) && !d_matched)
+        return fail(VX_EINVAL, std::string(who) + ": expected rows without d_matched");
+    if ((reinterpret_cast<uintptr_t>(d_base) | reinterpret_cast<uintptr_t>(d_work) |
+         reinterpret_cast<uintptr_t>(d_roots)) & 15)
+        return fail(VX_EINVAL, std::string(who) + ": d_base, d_work and d_roots must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(d_sha1) | reinterpret_cast<uintptr_t>(d_exp_sha1) |
+         reinterpret_cast<uintptr_t>(d_exp_roots)) & 3)
+        return fail(VX_EINVAL, std::string(who) + ": d_sha1 and the expected rows must be 4-byte aligned");
+    if (((uint64_t)n << log2_width) >> 32)
+        return fail(VX_EINVAL, std::string(who) + ": n << log2_width does not fit 32 bits");
+    if (n == 0) return 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    uint8_t* w = static_cast<uint8_t*>(d_work);
+    uint8_t* tab = w + merkle_work_bytes(n, log2_width);
+    uint64_t* tail_offs = reinterpret_cast<uint64_t*>(tab);
+    uint64_t* poffs = tail_offs + n;
+    uint64_t* tlens = poffs + n;
+    uint32_t* clens = reinterpret_cast<uint32_t*>(tlens + n);
+    uint32_t* pids = clens + n;
+    uint32_t* states = pids + n;
+    uint8_t* v1 = reinterpret_cast<uint8_t*>(states + (size_t)5 * n);
+    uint8_t* v2 = v1 + n;
+    const uint8_t* exp1 = static_cast<const uint8_t*>(d_exp_sha1);
+    const uint8_t* exp2 = static_cast<const uint8_t*>(d_exp_roots);
+    const uint8_t* base = static_cast<const uint8_t*>(d_base);
+    hipError_t e = vx::launch_hybrid_prep(d_offsets, d_lens, d_pads, n, tail_offs, poffs, tlens, clens, pids, st);
+    if (e == hipSuccess)
+        e = vx::launch_chunk(base, d_offsets, clens, n, pids, poffs, tlens, states, static_cast<uint8_t*>(d_sha1),
+                             exp1, exp1 ? v1 : nullptr, st);
+    if (e == hipSuccess)
+        e = vx::launch_zero_tail(base, tail_offs, d_lens, d_pads, nullptr, n, (uint64_t)VX_MERKLE_BLOCK << log2_width,
+                                 states, static_cast<uint8_t*>(d_sha1), exp1, exp1 ? v1 : nullptr, st);
+    if (e == hipSuccess)
+        e = vx::launch_merkle_pieces(base, d_offsets, d_lens, d_log2w, n, log2_width, w,
+                                     static_cast<uint8_t*>(d_roots), exp2, exp2 ? v2 : nullptr, st);
+    if (e == hipSuccess && (exp1 || exp2))
+        e = vx::launch_hybrid_merge(exp1 ? v1 : nullptr, exp2 ? v2 : nullptr, n, static_cast<uint8_t*>(d_matched),
+                                    st);
+    if (e != hipSuccess) return hip_fail(e, "hybrid piece kernels launch");
+    return 0;
+}
+
+int vx_tuning_zero_tail_kernel(const void* d_base, const uint64_t* d_tail_offs, const uint32_t* d_lens,
+                               const uint32_t* d_pads, uint32_t n, uint64_t piece_length, const uint32_t* d_states,
+                               void* d_digests, void* stream) {
+    if (n && (!d_base || !d_tail_offs || !d_lens || !d_pads || !d_states || !d_digests))
+        return fail(VX_EINVAL, "vx_tuning_zero_tail_kernel: NULL argument");
+    if (piece_length == 0 || (piece_length & 63))
+        return fail(VX_EINVAL, "vx_tuning_zero_tail_kernel: piece_length must be a multiple of 64");
+    hipError_t e = vx::launch_zero_tail(static_cast<const uint8_t*>(d_base), d_tail_offs, d_lens, d_pads, nullptr, n,
+                                        piece_length, d_states, static_cast<uint8_t*>(d_digests), nullptr, nullptr,
+                                        static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : hip_fail(e, "vx_tuning_zero_tail_kernel");
+}
+
+int vx_tuning_chunk_kernel(const void* d_base, const uint64_t* d_offsets, const uint32_t* d_lens, uint32_t n,
+                           const uint32_t* d_pids, const uint64_t* d_poffs, const uint64_t* d_tlens,
+                           uint32_t* d_states, void* d_digests, void* stream) {
+    if (n && (!d_base || !d_offsets || !d_lens || !d_pids || !d_poffs || !d_tlens || !d_states || !d_digests))
+        return fail(VX_EINVAL, "vx_tuning_chunk_kernel: NULL argument");
+    hipError_t e = vx::launch_chunk(static_cast<const uint8_t*>(d_base), d_offsets, d_lens, n, d_pids, d_poffs, d_tlens,
+                                    d_states, static_cast<uint8_t*>(d_digests), nullptr, nullptr,
+                                    static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : hip_fail(e, "vx_tuning_chunk_kernel");
+}
+
+int64_t vx_hybrid_verify_files_range(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                                     uint32_t piece_length, const uint8_t* exp_sha1, const uint8_t* exp_roots,
+                                     size_t n_pieces, size_t first, size_t count, uint8_t* matched_out,
+                                     uint32_t io_threads) {
+    return hybrid_files_impl(c, paths, file_lengths, nfiles, piece_length, exp_sha1, exp_roots, n_pieces, first, count,
+                             matched_out, io_threads);
+}
+
+int64_t vx_hybrid_verify_files(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                               uint32_t piece_length, const uint8_t* exp_sha1, const uint8_t* exp_roots,
+                               size_t n_pieces, uint8_t* matched_out, uint32_t io_threads) {
+    return hybrid_files_impl(c, paths, file_lengths, nfiles, piece_length, exp_sha1, exp_roots, n_pieces, 0, n_pieces,
+                             matched_out, io_threads);
+}
+
+}  // extern "C"

@@ -67,6 +67,33 @@ hipError_t launch_chunk(const uint8_t* base, const uint64_t* offsets, const uint
                         const uint32_t* pids, const uint64_t* poffs, const uint64_t* tlens, uint32_t* states,
                         uint8_t* digests, const uint8_t* expected, uint8_t* matched, hipStream_t stream);
 
+// Zero-tail continuation of a hybrid torrent's padded v1 pieces
+// (sha1_tail_kernels.hip).  Lane j finishes piece pid =
+// pids[j] (NULL: j), lens[j] data bytes followed by pads[j] zero bytes,
+// lens[j] + pads[j] == piece_length: from states[pid*5..] (the state after the
+// lens[j] >> 6 whole data blocks; the IV when there are none, states is then
+// not read) through the lens[j] & 63 tail bytes at base + tail_offs[j]
+// (4-byte aligned), the zero blocks and the final padding block, to digests /
+// matched row pid (expected row pid).  A lane with pads[j] == 0 stores nothing.
+// TailSched: K(t) + W[t] of the final padding block of a total_len-byte
+// message, total_len a multiple of 64 (expanded on the host by tail_sched).
+struct TailSched {
+    uint32_t kw[80];
+};
+void tail_sched(uint64_t total_len, TailSched* out);
+hipError_t launch_zero_tail(const uint8_t* base, const uint64_t* tail_offs, const uint32_t* lens,
+                            const uint32_t* pads, const uint32_t* pids, uint32_t n, uint64_t piece_length,
+                            const uint32_t* states, uint8_t* digests, const uint8_t* expected, uint8_t* matched,
+                            hipStream_t stream);
+// vx_hybrid_device_pieces: launch_chunk's and launch_zero_tail's tables from
+// device-resident offsets / lens / pads, and the two verdicts into one byte
+// (bit 0 = v1, bit 1 = v2; either may be NULL).
+hipError_t launch_hybrid_prep(const uint64_t* offsets, const uint32_t* lens, const uint32_t* pads, uint32_t n,
+                              uint64_t* tail_offs, uint64_t* poffs, uint64_t* tlens, uint32_t* clens, uint32_t* pids,
+                              hipStream_t stream);
+hipError_t launch_hybrid_merge(const uint8_t* v1, const uint8_t* v2, uint32_t n, uint8_t* matched,
+                               hipStream_t stream);
+
 // Gather registered host pieces into a slot arena (vx_gather.hip, DESIGN.md
 // §6.5): piece i (16-byte aligned device-mapped source src[i], length
 // lens[i]) lands at arena + dst_off[i]; it owns 64 KiB tiles

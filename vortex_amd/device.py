@@ -344,6 +344,78 @@ def merkle_pieces(data: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor,
     return roots, matched
 
 
+def hybrid_work_bytes(n: int, log2_width: int) -> int:
+    """Bytes of the work tensor of :func:`hybrid_pieces` (vx_hash.h,
+    vx_hybrid_device_pieces): the merkle piece kernel's work rounded up to 16,
+    then 54 bytes per piece."""
+    w = ((n << (log2_width - 8)) * 32 + n + 15) // 16 * 16 if log2_width > 8 else 0
+    return w + 54 * n
+
+
+def hybrid_pieces(data: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor, pads: torch.Tensor,
+                  log2_width: int, log2w: Optional[torch.Tensor] = None, exp_sha1: Optional[torch.Tensor] = None,
+                  exp_roots: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                  validate: bool = True):
+    """The pieces of a hybrid (v1 + v2) torrent in one call over one buffer
+    (vx_hybrid_device_pieces): piece i is data[offsets[i] : offsets[i] +
+    lens[i]], its v1 digest is over those bytes followed by pads[i] zeros that
+    exist nowhere (pads[i] is 0 or (16384 << log2_width) - lens[i]; see
+    vortex_amd.hybrid.hybrid_pieces), its v2 root over the bytes alone as a
+    tree of 2^log2w[i] leaf slots.  offsets int64, lens and pads int32, log2w
+    uint8 device tensors; exp_sha1 [n,20] and exp_roots [n,32] uint8 or None.
+
+    Returns (sha1 [n,20], roots [n,32], matched [n] or None); matched has bit
+    0 set where the SHA-1 matches and bit 1 where the root does, and is None
+    when neither expected table is given.  Enqueue-only."""
+    _req(data, "data")
+    _req(offsets, "offsets", torch.int64)
+    _req(lens, "lens", torch.int32)
+    _req(pads, "pads", torch.int32)
+    n = offsets.numel()
+    if lens.numel() != n or pads.numel() != n:
+        raise ValueError("offsets, lens and pads differ in length")
+    if log2w is not None:
+        _req(log2w, "log2w")
+        if log2w.numel() != n:
+            raise ValueError("log2w must hold n widths")
+    dev = data.device
+    for name, t, row in (("offsets", offsets, 0), ("lens", lens, 0), ("pads", pads, 0), ("log2w", log2w, 0),
+                         ("exp_sha1", exp_sha1, 20), ("exp_roots", exp_roots, 32)):
+        if t is None:
+            continue
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, data on {dev}")
+        if row:
+            _req(t, name)
+            if t.numel() < row * n:
+                raise ValueError(f"{name} must hold n*{row} bytes")
+    if not 0 <= log2_width <= 17:
+        raise ValueError("log2_width must be 0..17")
+    if (n << log2_width) >> 32:
+        raise ValueError("n << log2_width must fit 32 bits")
+    if validate and n:
+        _check_merkle_layout(data, offsets, lens, log2w, log2_width, "hybrid_pieces")
+        total = lens.to(torch.int64) + pads.to(torch.int64)
+        if bool((pads.ne(0) & total.ne(16384 << log2_width)).any().item()) or bool(pads.lt(0).any().item()):
+            raise ValueError("hybrid_pieces: a pad is neither 0 nor (16384 << log2_width) - len")
+    sha1 = torch.empty((n, 20), dtype=torch.uint8, device=dev)
+    roots = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    matched = torch.empty((n,), dtype=torch.uint8, device=dev) if (exp_sha1 is not None or
+                                                                  exp_roots is not None) else None
+    work = torch.empty((max(16, hybrid_work_bytes(n, log2_width)),), dtype=torch.uint8, device=dev)
+    if stream is not None:  # the scratch outlives this call on the stream that uses it
+        work.record_stream(stream)
+    rc = lib().vx_hybrid_device_pieces(data.data_ptr(), offsets.data_ptr(), lens.data_ptr(), pads.data_ptr(),
+                                       log2w.data_ptr() if log2w is not None else None, n, log2_width,
+                                       work.data_ptr(), sha1.data_ptr(), roots.data_ptr(),
+                                       exp_sha1.data_ptr() if exp_sha1 is not None else None,
+                                       exp_roots.data_ptr() if exp_roots is not None else None,
+                                       matched.data_ptr() if matched is not None else None,
+                                       _stream_ptr(stream, dev))
+    check(rc, "vx_hybrid_device_pieces")
+    return sha1, roots, matched
+
+
 SKIP_ROW = 0xFFFFFFFF  # merkle_blocks: a block that stores no leaf row
 
 

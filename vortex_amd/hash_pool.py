@@ -487,6 +487,37 @@ class HashPool:
         bad = check(rc, "vx_merkle_verify_files", self.lib)
         return [bool(b) for b in out.raw[:count]], int(bad)
 
+    def verify_hybrid_files(self, paths: Sequence[str], file_lengths: Sequence[int], piece_length: int,
+                            pieces: bytes, roots: bytes, first: int = 0, count: int | None = None,
+                            io_threads: int = 0) -> list[tuple[bool, bool]]:
+        """Re-verify a hybrid (v1 + v2, BEP 52 "upgrade path") torrent from
+        disk in one pass (vx_hybrid_verify_files): `paths` / `file_lengths`
+        list the real files only, the BEP 47 pad files between them are
+        implied and never read; `pieces` is the v1 `pieces` table (n*20
+        bytes), `roots` what verify_merkle_files takes (n*32 bytes), pieces
+        numbered as hybrid.hybrid_pieces numbers them.  Every byte is read and
+        copied to the device once and feeds both hashes.  Returns one
+        (v1_ok, v2_ok) per piece of [first, first+count); a piece that could
+        not be read is (False, False) and counts in stats()["io_errors"]."""
+        n = len(roots) // 32
+        if len(pieces) != 20 * n or len(roots) != 32 * n:
+            raise ValueError("pieces holds 20 bytes and roots 32 bytes per piece")
+        if count is None:
+            count = n - first
+        arr = (ctypes.c_char_p * max(1, len(paths)))(*[os.fsencode(p) for p in paths])
+        lens = (ctypes.c_uint64 * max(1, len(file_lengths)))(*file_lengths)
+        exp1 = ctypes.create_string_buffer(bytes(pieces), max(1, len(pieces)))
+        exp2 = ctypes.create_string_buffer(bytes(roots), max(1, len(roots)))
+        out = ctypes.create_string_buffer(max(1, count))
+        if first == 0 and count == n:
+            rc = self.lib.vx_hybrid_verify_files(self._h, arr, lens, len(paths), piece_length, exp1, exp2, n, out,
+                                                 io_threads)
+        else:
+            rc = self.lib.vx_hybrid_verify_files_range(self._h, arr, lens, len(paths), piece_length, exp1, exp2, n,
+                                                       first, count, out, io_threads)
+        check(rc, "vx_hybrid_verify_files", self.lib)
+        return [(bool(b & 1), bool(b & 2)) for b in out.raw[:count]]
+
 
 def _verify_files(pool: "HashPool", paths: Sequence[str], file_lengths: Sequence[int], piece_length: int,
                   expected: bytes, io_threads: int = 0, first: int = 0,
