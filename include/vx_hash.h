@@ -703,6 +703,64 @@ int64_t vx_hybrid_verify_files_range(vx_ctx* ctx, const char* const* paths, cons
                                      const uint8_t* exp_roots, size_t n_pieces, size_t first, size_t count,
                                      uint8_t* matched_out, uint32_t io_threads);
 
+/* The hybrid download path: vx_submit / vx_poll for a piece of a hybrid
+ * torrent.  One submit, one transfer and one completion give both hashes, in
+ * place of vx_submit over a caller-made copy with the pad zeros appended plus
+ * vx_merkle_submit, two slots and two completions to join.  `matched` holds the
+ * verdict bits of the entries above (bit 0: SHA-1, bit 1: root; 3 = good). */
+typedef struct vx_hybrid_completion {
+    uint64_t tag;
+    uint8_t matched;            /* bit 0: SHA-1 equal, bit 1: root equal */
+    uint8_t _pad[3];
+    uint8_t sha1[VX_DIGEST_LEN];  /* of data || pad_len zeros */
+    uint8_t root[VX_SHA256_LEN];
+} vx_hybrid_completion; /* 64 bytes */
+/* Queue data[0..len), the piece's bytes on disk.  Its SHA-1 is taken over
+ * those bytes followed by pad_len implied zeros (the BEP 47 pad behind a
+ * file's last piece, hashed without being read from anywhere); its merkle tree
+ * has 2^log2w leaf slots over data alone.  As vx_merkle_submit: len <=
+ * VX_MERKLE_BLOCK << log2w, log2w <= VX_MERKLE_MAX_LOG2_WIDTH and the tree no
+ * wider than max_piece_len rounded up to a power of two (VX_EINVAL); len >
+ * max_piece_len is VX_ERANGE.  pad_len is 0, or len > 0 and len + pad_len is a
+ * power of two >= VX_MERKLE_BLOCK, >= VX_MERKLE_BLOCK << log2w and <=
+ * max_piece_len rounded up to a power of two (VX_EINVAL otherwise).
+ * exp_sha1 (20 bytes) and exp_root (32 bytes) may each be NULL: a side's bit
+ * is set iff that side was given and equal, exactly (a side not given is not
+ * compared with anything); the digest and the root are always returned.
+ * Everything else is vx_submit's: the ownership rule (the piece is taken iff
+ * the call returns 0), every return code, VX_EBUSY under refuse_when_full, and
+ * the placement (registered and 16-byte aligned: gathered; registered and
+ * unaligned: copied straight from the caller's buffer; plain memory: through
+ * the pinned stage).  v1, v2 and hybrid pieces share the context's batch
+ * slots, pending count, vx_flush, vx_drain, the lazy flush, the sticky failure
+ * and the statistics (pieces_mismatched counts a piece once when any compared
+ * side fails, bytes_completed counts len).  A slot holds one kind, and within
+ * the hybrid kind one padded total (len + pad_len of its padded pieces): a
+ * change of either launches the open batch.  A hybrid slot is always copied or
+ * gathered into HBM first (never hashed zero-copy) and both hashes read that
+ * one copy: the merkle piece path runs on a stream of its own beside the SHA-1
+ * kernel over the whole data blocks, and one kernel then finishes the padded
+ * pieces' chains and compares both hashes. */
+int vx_hybrid_submit(vx_ctx* ctx, uint64_t tag, const uint8_t* data, uint32_t len, uint32_t pad_len,
+                     uint32_t log2w, const uint8_t* exp_sha1, const uint8_t* exp_root);
+/* Device-resident expected tables for hybrid pieces: the v1 `pieces` table
+ * (n_pieces x 20 bytes) and the v2 rows (n_pieces x 32 bytes, in the numbering
+ * of vx_hybrid_verify_files), uploaded once.  Replaces any earlier hybrid
+ * tables, is independent of vx_set_piece_table, and requires no pieces in
+ * flight (VX_EBUSY). */
+int vx_hybrid_set_piece_tables(vx_ctx* ctx, const uint8_t* sha1_table, const uint8_t* roots_table,
+                               uint32_t n_pieces);
+/* vx_hybrid_submit with both expected rows = row piece_index of the hybrid
+ * tables (both sides compared); an index outside the tables is VX_EINVAL.
+ * Table-indexed and explicit pieces do not share a slot. */
+int vx_hybrid_submit_piece(vx_ctx* ctx, uint64_t tag, const uint8_t* data, uint32_t len, uint32_t pad_len,
+                           uint32_t log2w, uint32_t piece_index);
+/* vx_poll for hybrid pieces: vx_poll hands out v1 completions only,
+ * vx_merkle_poll v2 only, this call hybrid only.  After a device failure each
+ * returns the results it still holds, then the error.  Bulk calls return
+ * VX_EBUSY while hybrid pieces are pending (the shared count). */
+int64_t vx_hybrid_poll(vx_ctx* ctx, vx_hybrid_completion* out, size_t max);
+
 /* ---- v2 metadata: `piece layers` and hash proofs in batches -------------
  * Every entry above takes its expected rows on trust.  BEP 52 says how a
  * client earns that trust: a file's `piece layers` string must reduce to the

@@ -57,6 +57,7 @@ EXPORTS = (
     "vx_merkle_layers_plan", "vx_merkle_device_layers", "vx_merkle_device_proofs", "vx_merkle_verify_layers",
     "vx_merkle_verify_proofs",
     "vx_hybrid_device_pieces", "vx_hybrid_verify_files", "vx_hybrid_verify_files_range",
+    "vx_hybrid_submit", "vx_hybrid_set_piece_tables", "vx_hybrid_submit_piece", "vx_hybrid_poll",
 )
 # ... plus include/vx_tuning.h and include/vx_synth.h: libvortex_amd_tuning.so only.
 TUNING_EXPORTS = (
@@ -86,6 +87,12 @@ class vx_merkle_completion(ctypes.Structure):
     """A v2 piece's completion (vx_merkle_poll): 48 bytes."""
     _fields_ = [("tag", ctypes.c_uint64), ("matched", ctypes.c_uint8), ("root", ctypes.c_uint8 * 32),
                 ("_pad", ctypes.c_uint8 * 7)]
+
+
+class vx_hybrid_completion(ctypes.Structure):
+    """A hybrid piece's completion (vx_hybrid_poll): 64 bytes; matched bit 0 = SHA-1, bit 1 = root."""
+    _fields_ = [("tag", ctypes.c_uint64), ("matched", ctypes.c_uint8), ("_pad", ctypes.c_uint8 * 3),
+                ("sha1", ctypes.c_uint8 * 20), ("root", ctypes.c_uint8 * 32)]
 
 
 VX_MERKLE_TILE_ROWS = 512
@@ -260,6 +267,10 @@ def _declare(L: ctypes.CDLL, tuning: bool = False) -> None:
                                    c.c_int64),
         "vx_hybrid_verify_files_range": ([vp, vp, vp, c.c_size_t, c.c_uint32, vp, vp, c.c_size_t, c.c_size_t,
                                           c.c_size_t, vp, c.c_uint32], c.c_int64),
+        "vx_hybrid_submit": ([vp, c.c_uint64, vp, c.c_uint32, c.c_uint32, c.c_uint32, vp, vp], c.c_int),
+        "vx_hybrid_set_piece_tables": ([vp, vp, vp, c.c_uint32], c.c_int),
+        "vx_hybrid_submit_piece": ([vp, c.c_uint64, vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32], c.c_int),
+        "vx_hybrid_poll": ([vp, c.POINTER(vx_hybrid_completion), c.c_size_t], c.c_int64),
     }
     if tuning:
         sig.update({

@@ -173,6 +173,99 @@ __global__ __launch_bounds__(kBlock) void hybrid_merge_kernel(const uint8_t* __r
     matched[i] = (uint8_t)((v1 && v1[i] ? 1u : 0u) | (v2 && v2[i] ? 2u : 0u));
 }
 
+// The end of a hybrid download slot (vx_hybrid_submit), one
+// lane per piece: in place of the tail launch plus hybrid_merge_kernel, and
+// the one kernel that compares both hashes with rows named by an index.
+//   * A padded lane (pads[j] != 0) continues as sha1_zero_tail_kernel does, from
+//     states[5j..] (the IV when the piece has no whole block) through the
+//     mixed block, its zero blocks and the launch's final block (every padded
+//     piece of a launch has one total length), and writes digest row j.
+//   * An unpadded lane's digest row was written by the chunked kernel.
+//   * Every lane < n then compares its digest and its root (row j of roots,
+//     from the merkle path) with row r of exp_sha1 / exp_roots, r =
+//     exp_index[j] or j, and writes matched[j]: bit 0 = SHA-1 equal and
+//     flags[j] bit 0, bit 1 = root equal and flags[j] bit 1.  A side whose
+//     flag bit is clear is not read.
+// A wave with no padded lane skips the SHA-1 part.  Lanes past n redo lane
+// n - 1 (in bounds) and store nothing.
+__global__ __launch_bounds__(kTailBlock) void hybrid_finish_kernel(
+    const uint8_t* __restrict__ base, const uint64_t* __restrict__ tail_offs, const uint32_t* __restrict__ lens,
+    const uint32_t* __restrict__ pads, uint32_t n, const uint32_t* __restrict__ states, uint8_t* digests,
+    const uint8_t* __restrict__ roots, const uint8_t* __restrict__ exp_sha1, const uint8_t* __restrict__ exp_roots,
+    const uint32_t* __restrict__ exp_index, const uint8_t* __restrict__ flags, uint8_t* __restrict__ matched,
+    const TailSched fin) {
+    const uint32_t j = blockIdx.x * kTailBlock + threadIdx.x;
+    const uint32_t jj = j < n ? j : n - 1;
+    const uint32_t len = lens[jj], pad = pads[jj];
+    const bool live = j < n && pad != 0;
+    const uint32_t rem = live ? len & 63u : 0u;
+    const uint32_t fill = rem ? 64u - rem : 0u;  // zeros that complete the mixed block
+    const uint32_t z = live && pad >= fill ? (pad - fill) >> 6 : 0u;
+    const uint32_t z_wave = __builtin_amdgcn_readfirstlane(tail_wave_max(z));
+    const uint32_t any_pad = __builtin_amdgcn_readfirstlane(tail_wave_max(live ? 1u : 0u));
+
+    State s = iv();
+    if (any_pad) {  // wave-uniform
+        if (live && (len >> 6)) {
+            const uint32_t* st = states + (size_t)jj * 5;
+            s = State{st[0], st[1], st[2], st[3], st[4]};
+        }
+        if (rem) {
+            // (as sha1_zero_tail_kernel: only the aligned words that hold a tail byte, the last one masked)
+            const uint32_t* q32 = reinterpret_cast<const uint32_t*>(base + tail_offs[jj]);
+            uint32_t w[16];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const uint32_t off = 4u * k;
+                uint32_t v = off < rem ? q32[k] : 0u;
+                if (rem - off < 4u) v &= (1u << (8u * (rem - off))) - 1u;
+                w[k] = bswap(v);
+            }
+            compress(s, w);
+        }
+        for (uint32_t b = 0; b < z_wave; ++b) {
+            State t = s;
+            compress_known(t, ZeroWords{});
+            const bool mine = b < z;
+            s.h0 = mine ? t.h0 : s.h0;
+            s.h1 = mine ? t.h1 : s.h1;
+            s.h2 = mine ? t.h2 : s.h2;
+            s.h3 = mine ? t.h3 : s.h3;
+            s.h4 = mine ? t.h4 : s.h4;
+        }
+        compress_known(s, FinalWords{fin});
+    }
+    if (j >= n) return;
+    uint32_t* dg = reinterpret_cast<uint32_t*>(digests + (size_t)j * 20);
+    uint32_t d0, d1, d2, d3, d4;
+    if (live) {
+        d0 = bswap(s.h0), d1 = bswap(s.h1), d2 = bswap(s.h2), d3 = bswap(s.h3), d4 = bswap(s.h4);
+        dg[0] = d0;
+        dg[1] = d1;
+        dg[2] = d2;
+        dg[3] = d3;
+        dg[4] = d4;
+    } else {
+        d0 = dg[0], d1 = dg[1], d2 = dg[2], d3 = dg[3], d4 = dg[4];
+    }
+    const uint32_t fl = flags[j];
+    const size_t row = exp_index ? exp_index[j] : j;
+    uint32_t verdict = 0;
+    if (fl & 1u) {
+        const uint32_t* x = reinterpret_cast<const uint32_t*>(exp_sha1 + row * 20);
+        verdict |= ((x[0] == d0) & (x[1] == d1) & (x[2] == d2) & (x[3] == d3) & (x[4] == d4)) ? 1u : 0u;
+    }
+    if (fl & 2u) {
+        const uint32_t* r = reinterpret_cast<const uint32_t*>(roots + (size_t)j * 32);
+        const uint32_t* x = reinterpret_cast<const uint32_t*>(exp_roots + row * 32);
+        uint32_t diff = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) diff |= r[k] ^ x[k];
+        verdict |= diff == 0 ? 2u : 0u;
+    }
+    matched[j] = (uint8_t)verdict;
+}
+
 void tail_sched(uint64_t total_len, TailSched* out) {
     uint32_t w[80] = {};
     w[0] = 0x80000000u;
@@ -195,6 +288,20 @@ hipError_t launch_zero_tail(const uint8_t* base, const uint64_t* tail_offs, cons
     const uint32_t blocks = (n + kTailBlock - 1) / kTailBlock;
     hipLaunchKernelGGL(sha1_zero_tail_kernel, dim3(blocks), dim3(kTailBlock), 0, stream, base, tail_offs, lens, pads,
                        pids, n, states, digests, expected, matched, fin);
+    return hipGetLastError();
+}
+
+hipError_t launch_hybrid_finish(const uint8_t* base, const uint64_t* tail_offs, const uint32_t* lens,
+                                const uint32_t* pads, uint32_t n, uint64_t padded_total, const uint32_t* states,
+                                uint8_t* digests, const uint8_t* roots, const uint8_t* exp_sha1,
+                                const uint8_t* exp_roots, const uint32_t* exp_index, const uint8_t* flags,
+                                uint8_t* matched, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    TailSched fin;
+    tail_sched(padded_total, &fin);  // (unused when no piece of the launch is padded)
+    const uint32_t blocks = (n + kTailBlock - 1) / kTailBlock;
+    hipLaunchKernelGGL(hybrid_finish_kernel, dim3(blocks), dim3(kTailBlock), 0, stream, base, tail_offs, lens, pads, n,
+                       states, digests, roots, exp_sha1, exp_roots, exp_index, flags, matched, fin);
     return hipGetLastError();
 }
 

@@ -5,6 +5,8 @@
 //    (peer_connection.rs:1145-1158 → torrent.rs:415-442), batched for the GPU.
 //  * vx_merkle_submit / vx_merkle_poll: the same cycle for a BitTorrent v2
 //    piece (a SHA-256 merkle root), through the same slots and placement.
+//  * vx_hybrid_submit / vx_hybrid_poll: the same cycle for a piece of a hybrid
+//    torrent, both hashes from one submit (the launch: vx_hybrid.hip).
 //  * vx_sha1_batch / vx_verify_batch: the par_iter bulk verify
 //    (torrent.rs:724-740).
 //  * vx_sha1_device_*: enqueue the kernels on device-resident batches.
@@ -130,6 +132,9 @@ int free_slot_mem(Slot& s) {
     if (s.d_v2) (void)hipFree(s.d_v2);
     if (s.h_v2) (void)hipHostFree(s.h_v2);
     if (s.d_tops) (void)hipFree(s.d_tops);
+    if (s.d_hy) (void)hipFree(s.d_hy);
+    if (s.h_hy) (void)hipHostFree(s.h_hy);
+    if (s.hy_joined) (void)hipEventDestroy(s.hy_joined);
     free_stage(s);
     if (s.h_meta) (void)hipHostFree(s.h_meta);
     s = Slot{};
@@ -211,6 +216,26 @@ int ensure_v2(Slot& s) {
     return 0;
 }
 
+// The hybrid buffers of slot s (vx_hybrid_submit), allocated on its first
+// hybrid piece, beside the v2 block that takes the roots.
+int ensure_hybrid(Slot& s) {
+    if (int rc = ensure_v2(s)) return rc;
+    if (s.h_hy) return 0;
+    const size_t bytes = vx_hybrid_slot::pack(s.cap).bytes;
+    uint8_t *h = nullptr, *d = nullptr;
+    hipEvent_t ev = nullptr;
+    if (hipHostMalloc(&h, bytes, hipHostMallocDefault) != hipSuccess || hipMalloc(&d, bytes) != hipSuccess ||
+        hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+        if (h) (void)hipHostFree(h);
+        if (d) (void)hipFree(d);
+        return fail(VX_ENOMEM, "vx_hybrid_submit: hybrid metadata allocation failed");
+    }
+    s.h_hy = h;
+    s.d_hy = d;
+    s.hy_joined = ev;
+    return 0;
+}
+
 void reset_fill(Slot& s) {
     s.tags.clear();
     s.runs.clear();
@@ -226,6 +251,10 @@ void reset_fill(Slot& s) {
     s.use_table = false;
     s.v2 = false;
     s.v2_kmax = 0;
+    s.hybrid = false;
+    s.hy_total = 0;
+    s.hy_lanes.clear();
+    s.hy_rows.clear();
     s.all_mapped = true;
 }
 
@@ -379,6 +408,7 @@ int launch_slot_impl(vx_ctx* c, int si) {
         s.state = Slot::FREE;
         return 0;
     }
+    if (s.hybrid) return launch_hybrid_slot(c, si);  // vx_hybrid.hip: never zero-copy, its own sequence
     hipStream_t cs = s.stream;
     // Zero-copy slot: every piece is read by the hash kernel itself, so no
     // bytes cross PCIe ahead of it and nothing waits for the copy chain.
@@ -502,6 +532,17 @@ void harvest(vx_ctx* c, Slot& s) {
     uint64_t bytes = 0, bad = 0;
     for (uint32_t i = 0; i < s.n; ++i) {
         const uint8_t matched = s.has_expected ? s.h_matched[i] : 0;
+        if (s.hybrid) {
+            vx_hybrid_completion r{};
+            r.tag = s.tags[i];
+            r.matched = matched;
+            std::memcpy(r.sha1, s.h_digests + (size_t)i * 20, 20);
+            std::memcpy(r.root, s.h_roots + (size_t)i * 32, 32);
+            c->done_hy.push_back(r);
+            bytes += s.h_lens[i];
+            bad += (s.hy_lanes[i].flags & ~matched) != 0;  // once, when any compared side fails
+            continue;
+        }
         if (s.v2) {
             vx_merkle_completion r{};
             r.tag = s.tags[i];
@@ -590,8 +631,11 @@ int acquire_filling(vx_ctx* c, bool may_wait = true) {
 // compare with row piece_row of the device piece table.
 // v2_log2w >= 0: a v2 piece (vx_merkle_submit) of 2^v2_log2w leaf slots,
 // `expected` its 32-byte root; placement, ownership and errors are the same.
+// hy: a hybrid piece (vx_hybrid_submit) of hy->pad_len implied zeros and 2^hy->log2w
+// leaf slots, `expected` its SHA-1 row and hy->exp_root its root (piece_row >= 0:
+// row piece_row of the two hybrid tables).
 int submit_impl(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, const uint8_t* expected,
-                int64_t piece_row, int v2_log2w) {
+                int64_t piece_row, int v2_log2w, const HybridPiece* hy) {
     if (c->sticky) return c->sticky;
     if (!data && len) return fail(VX_EINVAL, "vx_submit: data is NULL");
     if (len > c->cfg.max_piece_len) return fail(VX_ERANGE, "vx_submit: piece longer than max_piece_len");
@@ -601,6 +645,9 @@ int submit_impl(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, cons
 #endif
     const bool table = piece_row >= 0;
     const bool v2 = v2_log2w >= 0;
+    const bool hybrid = hy != nullptr;
+    const uint32_t tree_log2w = hybrid ? hy->log2w : (uint32_t)std::max(v2_log2w, 0);
+    const uint64_t hy_total = hybrid && hy->pad_len ? (uint64_t)len + hy->pad_len : 0;
     const bool may_wait = !c->cfg.refuse_when_full || c->bulk;  // host batches always wait
     int si = acquire_filling(c, may_wait);
     if (si < 0) return si;
@@ -608,9 +655,12 @@ int submit_impl(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, cons
     uint64_t off = align_up(s->bytes, kAlign);
     // the piece kernel runs (pieces << widest log2w) lanes, a 32-bit count
     const bool v2_lanes_full =
-        v2 && ((uint64_t)(s->n + 1) << std::max<uint32_t>(s->v2_kmax, (uint32_t)v2_log2w)) > (1ull << 31);
-    // a slot holds either table-indexed or explicit-digest pieces, and either v1 or v2 pieces
-    if (s->n == s->cap || off + len > s->arena_cap || (s->n && (s->use_table != table || s->v2 != v2)) ||
+        (v2 || hybrid) && ((uint64_t)(s->n + 1) << std::max<uint32_t>(s->v2_kmax, tree_log2w)) > (1ull << 31);
+    // a slot holds either table-indexed or explicit-digest pieces, and one kind: v1, v2 or hybrid;
+    // a hybrid slot's padded pieces have one total length (the finish kernel's final block)
+    const bool other_total = hy_total && s->hy_total && s->hy_total != hy_total;
+    if (s->n == s->cap || off + len > s->arena_cap ||
+        (s->n && (s->use_table != table || s->v2 != v2 || s->hybrid != hybrid || other_total)) ||
         (s->n && v2_lanes_full)) {
         int rc = launch_slot(c, si);
         if (rc) return rc;
@@ -623,6 +673,8 @@ int submit_impl(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, cons
     const uint8_t* dev = nullptr;
     if (v2)
         if (int rc = ensure_v2(*s)) return rc;
+    if (hybrid)
+        if (int rc = ensure_hybrid(*s)) return rc;
     s->h_src[i] = 0;
     if (i == 0) s->t_open = std::chrono::steady_clock::now();
     if (len && (reinterpret_cast<uintptr_t>(data) & 15) == 0 && is_registered(c, data, len, &dev)) {
@@ -674,7 +726,23 @@ int submit_impl(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, cons
         s->h_log2w[i] = (uint8_t)v2_log2w;
         s->v2_kmax = std::max<uint32_t>(s->v2_kmax, (uint32_t)v2_log2w);
     }
-    if (table) {
+    if (hybrid) {
+        // The verdict column always comes back; which sides were given is the
+        // lane's flags, so a side's bit is exact and not "compared with a zero row".
+        Slot::HybridRows rows{};
+        if (expected) std::memcpy(rows.sha1, expected, VX_DIGEST_LEN);
+        if (hy->exp_root) std::memcpy(rows.root, hy->exp_root, VX_SHA256_LEN);
+        rows.log2w = (uint8_t)hy->log2w;
+        const uint8_t flags = table ? 3 : (uint8_t)((expected ? 1 : 0) | (hy->exp_root ? 2 : 0));
+        s->hy_rows.push_back(rows);
+        s->hy_lanes.push_back(vx_hybrid_slot::lane(off, len, hy->pad_len, flags));
+        s->hybrid = true;
+        s->v2_kmax = std::max<uint32_t>(s->v2_kmax, hy->log2w);
+        if (hy_total) s->hy_total = hy_total;
+        s->h_pidx[i] = table ? (uint32_t)piece_row : i;
+        s->use_table = table;
+        s->has_expected = true;
+    } else if (table) {
         s->h_pidx[i] = (uint32_t)piece_row;
         s->use_table = true;
         s->has_expected = true;
@@ -701,6 +769,10 @@ int submit_impl(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, cons
             // the caller with the error; the rest of the slot stays pending and
             // is what the caller recovers after vx_poll reports the failure.
             s->tags.pop_back();
+            if (hybrid) {
+                s->hy_lanes.pop_back();
+                s->hy_rows.pop_back();
+            }
             s->n = i;
             c->pending--;
             return rc;
@@ -1071,6 +1143,8 @@ int vx_destroy(vx_ctx* c) {
     // the re-verify's data copies run on the copy stream: a failed call may
     // have left one queued that still reads a stage or writes an arena
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+    // ... and a hybrid slot's merkle work on the side stream reads its arena
+    if (c->hy_stream) (void)hipStreamSynchronize(c->hy_stream);
     for (auto& r : c->registered) (void)hipHostUnregister(reinterpret_cast<void*>(r.first));
     for (auto& s : c->slots) free_slot_mem(s);
     if (c->d_table) (void)hipFree(c->d_table);
@@ -1086,6 +1160,9 @@ int vx_destroy(vx_ctx* c) {
         if (e) (void)hipEventDestroy(e);
     if (c->anchor_ev) (void)hipEventDestroy(c->anchor_ev);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
+    if (c->hy_stream) (void)hipStreamDestroy(c->hy_stream);
+    if (c->d_hy_sha1) (void)hipFree(c->d_hy_sha1);
+    if (c->d_hy_roots) (void)hipFree(c->d_hy_roots);
     delete c;
     return rc;
 }
@@ -1199,6 +1276,60 @@ int vx_merkle_submit(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len,
     int rc = set_device(c);
     if (rc) return rc;
     return submit_impl(c, tag, data, len, expected, -1, (int)log2w);
+}
+
+int64_t vx_hybrid_poll(vx_ctx* c, vx_hybrid_completion* out, size_t max) {
+    if (!c || (!out && max)) return fail(VX_EINVAL, "vx_hybrid_poll: bad argument");
+    return poll_impl(c, c->done_hy, out, max);
+}
+
+static int hybrid_submit(vx_ctx* c, const char* who, uint64_t tag, const uint8_t* data, uint32_t len, uint32_t pad_len,
+                         uint32_t log2w, const uint8_t* exp_sha1, const uint8_t* exp_root, int64_t row) {
+    const char* why = nullptr;
+    if (int rc = vx_hybrid_slot::check(len, pad_len, log2w, c->cfg.max_piece_len, &why))
+        return fail(rc, std::string(who) + ": " + why);
+    int rc = set_device(c);
+    if (rc) return rc;
+    const HybridPiece hy{pad_len, log2w, exp_root};
+    return submit_impl(c, tag, data, len, exp_sha1, row, -1, &hy);
+}
+
+int vx_hybrid_submit(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, uint32_t pad_len, uint32_t log2w,
+                     const uint8_t* exp_sha1, const uint8_t* exp_root) {
+    if (!c) return fail(VX_EINVAL, "vx_hybrid_submit: NULL context");
+    return hybrid_submit(c, "vx_hybrid_submit", tag, data, len, pad_len, log2w, exp_sha1, exp_root, -1);
+}
+
+int vx_hybrid_submit_piece(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, uint32_t pad_len,
+                           uint32_t log2w, uint32_t piece_index) {
+    if (!c) return fail(VX_EINVAL, "vx_hybrid_submit_piece: NULL context");
+    if (piece_index >= c->n_hy_table)
+        return fail(VX_EINVAL, "vx_hybrid_submit_piece: piece_index outside the hybrid piece tables");
+    return hybrid_submit(c, "vx_hybrid_submit_piece", tag, data, len, pad_len, log2w, nullptr, nullptr,
+                         (int64_t)piece_index);
+}
+
+int vx_hybrid_set_piece_tables(vx_ctx* c, const uint8_t* sha1_table, const uint8_t* roots_table, uint32_t n_pieces) {
+    if (!c || (n_pieces && (!sha1_table || !roots_table)))
+        return fail(VX_EINVAL, "vx_hybrid_set_piece_tables: bad argument");
+    if (c->pending || c->filling >= 0) return fail(VX_EBUSY, "vx_hybrid_set_piece_tables: pieces in flight");
+    int rc = set_device(c);
+    if (rc) return rc;
+    if (c->d_hy_sha1) (void)hipFree(c->d_hy_sha1);
+    if (c->d_hy_roots) (void)hipFree(c->d_hy_roots);
+    c->d_hy_sha1 = c->d_hy_roots = nullptr;
+    c->n_hy_table = 0;
+    if (!n_pieces) return 0;
+    if (hipMalloc(&c->d_hy_sha1, (size_t)n_pieces * 20) != hipSuccess ||
+        hipMalloc(&c->d_hy_roots, (size_t)n_pieces * 32) != hipSuccess) {
+        if (c->d_hy_sha1) (void)hipFree(c->d_hy_sha1);
+        c->d_hy_sha1 = c->d_hy_roots = nullptr;
+        return fail(VX_ENOMEM, "vx_hybrid_set_piece_tables: device allocation failed");
+    }
+    VX_HIP(hipMemcpy(c->d_hy_sha1, sha1_table, (size_t)n_pieces * 20, hipMemcpyHostToDevice));
+    VX_HIP(hipMemcpy(c->d_hy_roots, roots_table, (size_t)n_pieces * 32, hipMemcpyHostToDevice));
+    c->n_hy_table = n_pieces;
+    return 0;
 }
 
 int vx_drain(vx_ctx* c, uint32_t timeout_ms) {

@@ -27,6 +27,7 @@
 
 #include "vx_files.hpp"
 #include "vx_hash.h"
+#include "vx_hybrid_slot.hpp"
 #include "vx_kernels.h"
 #include "vx_merkle_rounds.hpp"
 #include "vx_synth.h"
@@ -112,6 +113,22 @@ struct Slot {
     // their log2w), grown when a launch needs more
     uint8_t* d_tops = nullptr;
     uint64_t tops_cap = 0;
+    // hybrid pieces (vx_hybrid_submit), allocated on the slot's first hybrid
+    // use (ensure_hybrid): one pinned and one device block that hold a launch's
+    // whole metadata (vx_hybrid_slot::Pack; the SHA-1 states behind it on the
+    // device), and the event that joins the merkle side stream.  The roots land
+    // in the v2 block.  hy_lanes / hy_rows: what the submits filled in, packed
+    // at launch.
+    uint8_t* h_hy = nullptr;
+    uint8_t* d_hy = nullptr;
+    hipEvent_t hy_joined = nullptr;
+    struct HybridRows {
+        uint8_t sha1[VX_DIGEST_LEN], root[VX_SHA256_LEN], log2w;
+    };
+    std::vector<vx_hybrid_slot::Lane> hy_lanes;
+    std::vector<HybridRows> hy_rows;
+    bool hybrid = false;    // the slot's pieces are hybrid: a slot holds one kind
+    uint64_t hy_total = 0;  // ... and one padded total (len + pad_len of its padded pieces; 0: none yet)
     std::vector<uint64_t> tags;
     std::vector<Run> runs;
     std::vector<DirectRun> druns;
@@ -158,6 +175,15 @@ struct vx_ctx {
     bool bulk = false;  // inside vx_*_batch: slots fill to capacity, not to batch_pieces
     std::deque<vx_completion> done;
     std::deque<vx_merkle_completion> done_v2;  // v2 pieces' results (vx_merkle_poll)
+    std::deque<vx_hybrid_completion> done_hy;  // hybrid pieces' results (vx_hybrid_poll)
+    // Hybrid download path: the device-resident v1 `pieces`
+    // table and v2 rows (vx_hybrid_set_piece_tables), and the one side stream
+    // every hybrid slot's merkle work runs on, beside the slot's SHA-1 chain;
+    // created on the first hybrid launch.
+    uint8_t* d_hy_sha1 = nullptr;
+    uint8_t* d_hy_roots = nullptr;
+    uint32_t n_hy_table = 0;
+    hipStream_t hy_stream = nullptr;
     struct Reg {
         size_t len;
         uint8_t* dev;  // device mapping of the range (hipHostGetDevicePointer)
@@ -306,8 +332,14 @@ int chain_h2d(vx_ctx* c, int si);
 void mark_launched(vx_ctx* c, int si);
 int launch_slot(vx_ctx* c, int si);
 int reap(vx_ctx* c, bool block_oldest);
+// hy != nullptr: a hybrid piece (vx_hybrid_submit); `expected` is then its SHA-1 row.
+struct HybridPiece {
+    uint32_t pad_len, log2w;
+    const uint8_t* exp_root;
+};
 int submit_impl(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, const uint8_t* expected,
-                int64_t piece_row = -1, int v2_log2w = -1);
+                int64_t piece_row = -1, int v2_log2w = -1, const HybridPiece* hy = nullptr);
+int launch_hybrid_slot(vx_ctx* c, int si);  // vx_hybrid.hip: launch_slot_impl's branch for a hybrid slot
 void abandon_batch(vx_ctx* c);
 void release_filling_slots(vx_ctx* c);   // every FILLING slot (reserved, never launched) back to FREE
 void wait_and_free_inflight(vx_ctx* c);  // wait for every INFLIGHT slot, then free them unharvested

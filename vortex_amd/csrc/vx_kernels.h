@@ -94,6 +94,19 @@ hipError_t launch_hybrid_prep(const uint64_t* offsets, const uint32_t* lens, con
 hipError_t launch_hybrid_merge(const uint8_t* v1, const uint8_t* v2, uint32_t n, uint8_t* matched,
                                hipStream_t stream);
 
+// The end of a hybrid download slot (hybrid_finish_kernel):
+// lane j finishes piece j when pads[j] != 0 (as launch_zero_tail with pids =
+// NULL; every padded piece of the launch is padded_total bytes long, a
+// multiple of 64) into digests row j, then compares digests row j and roots
+// row j with row exp_index[j] (NULL: j) of exp_sha1 / exp_roots where
+// flags[j] bit 0 / bit 1 is set, and writes the two verdict bits to
+// matched[j].  A side whose flag bit is clear is not read.
+hipError_t launch_hybrid_finish(const uint8_t* base, const uint64_t* tail_offs, const uint32_t* lens,
+                                const uint32_t* pads, uint32_t n, uint64_t padded_total, const uint32_t* states,
+                                uint8_t* digests, const uint8_t* roots, const uint8_t* exp_sha1,
+                                const uint8_t* exp_roots, const uint32_t* exp_index, const uint8_t* flags,
+                                uint8_t* matched, hipStream_t stream);
+
 // Gather registered host pieces into a slot arena (vx_gather.hip, DESIGN.md
 // §6.5): piece i (16-byte aligned device-mapped source src[i], length
 // lens[i]) lands at arena + dst_off[i]; it owns 64 KiB tiles

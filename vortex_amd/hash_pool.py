@@ -17,7 +17,10 @@ reference                        here
 
 A BitTorrent v2 (BEP 52) piece takes the same path under
 :meth:`HashPool.spawn_merkle` / :meth:`HashPool.try_recv_merkle`: its result is
-the piece's SHA-256 merkle root (vx_merkle_submit / vx_merkle_poll).
+the piece's SHA-256 merkle root (vx_merkle_submit / vx_merkle_poll).  A piece
+of a hybrid (v1 + v2) torrent takes it once for both hashes under
+:meth:`HashPool.spawn_hybrid` / :meth:`HashPool.try_recv_hybrid`
+(vx_hybrid_submit / vx_hybrid_poll → :class:`DownloadedHybridPiece`).
 
 Semantics kept from the reference:
 * a hash mismatch is a value (``hash_matched=False``), never an exception;
@@ -49,6 +52,23 @@ class DownloadedPiece:
     hash_matched: bool
     buffer: Any
     digest: bytes = b""
+
+
+@dataclass
+class DownloadedHybridPiece:
+    """A hybrid (v1 + v2) piece's result (vx_hybrid_poll): ``matched`` has bit 0
+    set when the SHA-1 was given and equal and bit 1 when the root was."""
+
+    index: int
+    conn_id: int
+    matched: int
+    buffer: Any
+    sha1: bytes = b""
+    root: bytes = b""
+
+    @property
+    def hash_matched(self) -> bool:
+        return self.matched == 3
 
 
 def _addr_of(buf) -> tuple[int, Any]:
@@ -113,7 +133,9 @@ class HashPool:
         self._inflight: dict[int, tuple[int, int, Any, Any]] = {}
         self._cbuf = (vx_completion * 1024)()
         self._cbuf_v2 = (_lib.vx_merkle_completion * 1024)()
+        self._cbuf_hy = (_lib.vx_hybrid_completion * 1024)()
         self._registered: dict[int, tuple[int, Any, Any]] = {}  # id(buf) -> (address, keep-alive, buf)
+        self._hybrid_rows = 0  # rows of the tables given to set_hybrid_tables
 
     # -- lifecycle ---------------------------------------------------------
     def close(self) -> None:
@@ -219,6 +241,69 @@ class HashPool:
                 raise
         self._inflight[tag] = (index, conn_id, buffer, keep)
 
+    def spawn_hybrid(self, index: int, conn_id: int, buffer, piece_len: int, pad_len: int = 0,
+                     expected_sha1: Optional[bytes] = None, expected_root: Optional[bytes] = None,
+                     log2w: Optional[int] = None) -> None:
+        """spawn() for a piece of a hybrid (v1 + v2) torrent (vx_hybrid_submit):
+        one submit, one transfer and one result carry both hashes.  The SHA-1
+        is over buffer[:piece_len] followed by pad_len zeros that exist nowhere
+        (the BEP 47 pad behind a file's last piece, hybrid.hybrid_pieces), the
+        merkle root over buffer[:piece_len] alone as a tree of 2^log2w leaf
+        slots (default as spawn_merkle).  With both expected values None the
+        piece is compared with row `index` of the tables given to
+        set_hybrid_tables (vx_hybrid_submit_piece), or, when no tables are
+        set, with nothing: the hashes are only returned.  With one given, only
+        that side is compared.  The result comes back from try_recv_hybrid() /
+        try_iter_hybrid() only.  Ownership and errors as for spawn()."""
+        if expected_sha1 is not None and len(expected_sha1) != 20:
+            raise ValueError("expected_sha1 must be 20 bytes")
+        if expected_root is not None and len(expected_root) != 32:
+            raise ValueError("expected_root must be 32 bytes")
+        if log2w is None:
+            log2w = max(0, (int(self.config.max_piece_len) // _lib.VX_MERKLE_BLOCK).bit_length() - 1)
+        for name, value in (("piece_len", piece_len), ("pad_len", pad_len), ("log2w", log2w)):
+            if not 0 <= int(value) < 1 << 32:
+                raise ValueError(f"{name} outside the uint32 range")
+        by_index = expected_sha1 is None and expected_root is None and self._hybrid_rows > 0
+        if by_index and not 0 <= int(index) < 1 << 32:
+            raise ValueError("index outside the uint32 range")
+        if piece_len > memoryview(buffer).nbytes:
+            raise ValueError("piece_len exceeds buffer size")
+        addr, keep = _addr_of(buffer)
+        tag = self._next_tag
+        self._next_tag += 1
+        if by_index:
+            rc, where = self.lib.vx_hybrid_submit_piece(self._h, tag, addr, piece_len, int(pad_len), int(log2w),
+                                                        int(index)), "vx_hybrid_submit_piece"
+        else:
+            e1 = ctypes.create_string_buffer(bytes(expected_sha1), 20) if expected_sha1 is not None else None
+            e2 = ctypes.create_string_buffer(bytes(expected_root), 32) if expected_root is not None else None
+            rc, where = self.lib.vx_hybrid_submit(self._h, tag, addr, piece_len, int(pad_len), int(log2w), e1,
+                                                  e2), "vx_hybrid_submit"
+        if rc != 0:
+            try:
+                check(rc, where, self.lib)
+            except VxError as e:
+                e.refused = (index, conn_id, buffer)
+                raise
+        self._inflight[tag] = (index, conn_id, buffer, keep)
+
+    def set_hybrid_tables(self, pieces: bytes, roots: bytes) -> None:
+        """Upload a hybrid torrent's v1 `pieces` string (n x 20 B) and its v2
+        rows (n x 32 B, numbered as hybrid.hybrid_pieces numbers the pieces)
+        once (vx_hybrid_set_piece_tables); afterwards spawn_hybrid with no
+        expected values compares on the device by index.  Independent of
+        set_piece_table; needs nothing pending."""
+        if len(pieces) % 20 or len(roots) % 32 or len(pieces) // 20 != len(roots) // 32:
+            raise ValueError("pieces holds 20 bytes and roots 32 bytes per piece")
+        n = len(roots) // 32
+        if n >= 1 << 32:
+            raise ValueError("more than 2^32 - 1 pieces")
+        b1 = ctypes.create_string_buffer(bytes(pieces), max(1, len(pieces)))
+        b2 = ctypes.create_string_buffer(bytes(roots), max(1, len(roots)))
+        check(self.lib.vx_hybrid_set_piece_tables(self._h, b1, b2, n), "vx_hybrid_set_piece_tables", self.lib)
+        self._hybrid_rows = n
+
     def set_piece_table(self, pieces: bytes) -> None:
         """Upload the torrent's `pieces` string (n x 20 B) once; afterwards
         spawn(..., expected_hash=None) compares on the device by index."""
@@ -289,9 +374,39 @@ class HashPool:
             if len(got) < len(self._cbuf_v2):
                 return out
 
+    def _poll_hybrid(self, max_items: int) -> list[DownloadedHybridPiece]:
+        k = check(self.lib.vx_hybrid_poll(self._h, self._cbuf_hy, min(max_items, len(self._cbuf_hy))),
+                  "vx_hybrid_poll", self.lib)
+        out = []
+        for j in range(k):
+            r = self._cbuf_hy[j]
+            index, conn_id, buffer, _keep = self._inflight.pop(r.tag)
+            out.append(DownloadedHybridPiece(index, conn_id, int(r.matched), buffer, bytes(r.sha1), bytes(r.root)))
+        return out
+
+    def try_recv_hybrid(self) -> Optional[DownloadedHybridPiece]:
+        """try_recv() for hybrid pieces (vx_hybrid_poll).  Pieces given to
+        spawn() or spawn_merkle() never arrive here."""
+        got = self._poll_hybrid(1)
+        return got[0] if got else None
+
+    def try_iter_hybrid(self) -> list[DownloadedHybridPiece]:
+        """Every hybrid piece completed so far (try_iter() for spawn_hybrid)."""
+        out = []
+        while True:
+            try:
+                got = self._poll_hybrid(len(self._cbuf_hy))
+            except VxError:
+                if out:  # as try_iter: the error is sticky and the next call raises it
+                    return out
+                raise
+            out.extend(got)
+            if len(got) < len(self._cbuf_hy):
+                return out
+
     def take_unfinished(self) -> list[tuple[int, int, Any]]:
         """After a device error (a VxError from spawn / try_recv / try_iter, or
-        their _merkle forms; pieces of both kinds are listed):
+        their _merkle and _hybrid forms; pieces of all three kinds are listed):
         (index, conn_id, buffer) of every TAKEN piece whose result never came
         back, for the caller to hash on its own pool (INTEGRATION.md "Device
         failure").  A spawn that raised did not take its piece (it is in the
@@ -671,7 +786,7 @@ def piece_len(index: int, num_pieces: int, piece_length: int, total_length: int)
     return last if index == num_pieces - 1 else piece_length
 
 
-__all__ = ["DownloadedPiece", "HashPool", "verify_pieces", "verify_files_multi", "piece_len", "plan_verify",
+__all__ = ["DownloadedPiece", "DownloadedHybridPiece", "HashPool", "verify_pieces", "verify_files_multi", "piece_len", "plan_verify",
            "plan_verify_split"]
 
 
