@@ -175,8 +175,8 @@ def test_zero_copy_config1_shape(built, gpu):
                                                   (16384, 32, 1), (262144, 32, 1), (262144, 128, 0), (16384, 32, 0)])
 def test_zero_copy_default_policy(built, gpu, plen, batch, zero_copy):
     """With zero_copy = 1 (vx_config_default) a slot of registered aligned
-    pieces goes zero-copy at every length and batch size (vx_engine.hip
-    launch_slot_impl; small batches in the three-wave form) and never touches
+    pieces goes zero-copy at every length and batch size (vx_slots.hip
+    launch_v1; small batches in the three-wave form) and never touches
     the gather; with zero_copy = 0 the same pieces are gathered into HBM
     first.  Every digest and verdict is hashlib's either way."""
     from vortex_amd import _lib

@@ -1,15 +1,12 @@
-// vx_engine.hip — host side of the C ABI in include/vx_hash.h.
+// vx_engine.hip — the context behind the C ABI in include/vx_hash.h.
 //
-// Replaces, on the host, what vortex does around its hashing pool:
-//  * vx_submit / vx_flush / vx_poll: the scope.spawn → mpsc → try_recv cycle
-//    (peer_connection.rs:1145-1158 → torrent.rs:415-442), batched for the GPU.
-//  * vx_merkle_submit / vx_merkle_poll: the same cycle for a BitTorrent v2
-//    piece (a SHA-256 merkle root), through the same slots and placement.
-//  * vx_hybrid_submit / vx_hybrid_poll: the same cycle for a piece of a hybrid
-//    torrent, both hashes from one submit (the launch: vx_hybrid.hip).
+// The library replaces, on the host, what vortex does around its hashing pool:
+//  * vx_submit / vx_flush / vx_poll and their v2 and hybrid forms: the
+//    scope.spawn → mpsc → try_recv cycle (peer_connection.rs:1145-1158 →
+//    torrent.rs:415-442), batched for the GPU: the slot path, vx_slots.hip.
 //  * vx_sha1_batch / vx_verify_batch: the par_iter bulk verify
-//    (torrent.rs:724-740).
-//  * vx_sha1_device_*: enqueue the kernels on device-resident batches.
+//    (torrent.rs:724-740): here.
+//  * vx_sha1_device_*: enqueue the kernels on device-resident batches: here.
 //
 // Design (DESIGN.md "Host engine"): a context owns `slots` batch slots, each
 // with its own HIP stream, a device arena, a pinned staging arena and pinned
@@ -19,16 +16,16 @@
 // others go through the slot's pinned stage and move with one H2D per
 // contiguous run at launch.  On the async path (vx_submit) the stage copy is
 // a memcpy at submit; inside a host batch (vx_*_batch) the copies are
-// deferred to launch and split over up to 16 short-lived threads
-// (stage_copies), and the call waits for every slot before it returns.
-// A launch is H2D(meta) → kernel → D2H(digests, verdicts) → event; slots on
-// different streams overlap copy and compute.  vx_poll harvests finished
-// slots without blocking.  The async path has no internal threads: like the
+// deferred to launch and split over up to 16 short-lived threads, and the call
+// waits for every slot before it returns.  Slots on different streams overlap
+// copy and compute.  The async path has no internal threads: like the
 // reference's loop, it is driven from the caller's thread.
 //
-// This unit: context lifecycle, slots, the async path, host batches, stats,
-// vx_sha1_device_*.  The file re-verify is vx_reverify.hip, the split and the
-// planner vx_split.hip, BitTorrent v2 vx_merkle.hip (DESIGN.md "Host engine").
+// This unit: the error text, context lifecycle, slot and stage allocation and
+// warm-up, registration, host batches, stats, vx_sha1_device_*, the tuning and
+// synth entries.  The download path is vx_slots.hip, the file re-verify
+// vx_reverify.hip, the split and the planner vx_split.hip, BitTorrent v2
+// vx_merkle.hip, hybrid torrents vx_hybrid.hip (DESIGN.md "Host engine").
 #include "vx_chunk_pipe.hpp"
 
 namespace vxe {
@@ -44,9 +41,6 @@ int hip_fail(hipError_t e, const char* what) {
     g_err = std::string(what) + ": " + hipGetErrorString(e);
     return VX_EDEVICE;
 }
-
-// zc_loader_wins: the slot size below which a batch is latency-bound
-constexpr uint32_t kZcMinPieces = 128;
 
 // Pieces (lanes) a slot's metadata holds: the async batch size, or enough
 // chunk lanes to fill the arena with kMinChunk-byte chunks (the chunked paths
@@ -129,12 +123,12 @@ int free_slot_mem(Slot& s) {
     if (s.stream) (void)hipStreamDestroy(s.stream);
     if (s.d_arena) (void)hipFree(s.d_arena);
     if (s.d_meta) (void)hipFree(s.d_meta);
-    if (s.d_v2) (void)hipFree(s.d_v2);
-    if (s.h_v2) (void)hipHostFree(s.h_v2);
-    if (s.d_tops) (void)hipFree(s.d_tops);
-    if (s.d_hy) (void)hipFree(s.d_hy);
-    if (s.h_hy) (void)hipHostFree(s.h_hy);
-    if (s.hy_joined) (void)hipEventDestroy(s.hy_joined);
+    if (s.v2.d) (void)hipFree(s.v2.d);
+    if (s.v2.h) (void)hipHostFree(s.v2.h);
+    if (s.v2.d_tops) (void)hipFree(s.v2.d_tops);
+    if (s.hy.d) (void)hipFree(s.hy.d);
+    if (s.hy.h) (void)hipHostFree(s.hy.h);
+    if (s.hy.joined) (void)hipEventDestroy(s.hy.joined);
     free_stage(s);
     if (s.h_meta) (void)hipHostFree(s.h_meta);
     s = Slot{};
@@ -195,47 +189,6 @@ int ensure_stage(const vx_ctx* c, Slot& s) {
     return 0;
 }
 
-// The v2 buffers of slot s (vx_merkle_submit), allocated on its first v2 piece:
-// a context that only sees v1 pieces allocates nothing for v2.
-int ensure_v2(Slot& s) {
-    if (s.h_v2) return 0;
-    const size_t bytes = (size_t)s.cap * (32 + 32 + 1) + 64;
-    uint8_t *h = nullptr, *d = nullptr;
-    if (hipHostMalloc(&h, bytes, hipHostMallocDefault) != hipSuccess || hipMalloc(&d, bytes) != hipSuccess) {
-        if (h) (void)hipHostFree(h);
-        return fail(VX_ENOMEM, "vx_merkle_submit: v2 metadata allocation failed");
-    }
-    s.h_v2 = h;
-    s.d_v2 = d;
-    s.h_exp32 = h;
-    s.h_roots = h + (size_t)s.cap * 32;
-    s.h_log2w = h + (size_t)s.cap * 64;
-    s.d_exp32 = d;
-    s.d_roots = d + (size_t)s.cap * 32;
-    s.d_log2w = d + (size_t)s.cap * 64;
-    return 0;
-}
-
-// The hybrid buffers of slot s (vx_hybrid_submit), allocated on its first
-// hybrid piece, beside the v2 block that takes the roots.
-int ensure_hybrid(Slot& s) {
-    if (int rc = ensure_v2(s)) return rc;
-    if (s.h_hy) return 0;
-    const size_t bytes = vx_hybrid_slot::pack(s.cap).bytes;
-    uint8_t *h = nullptr, *d = nullptr;
-    hipEvent_t ev = nullptr;
-    if (hipHostMalloc(&h, bytes, hipHostMallocDefault) != hipSuccess || hipMalloc(&d, bytes) != hipSuccess ||
-        hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-        if (h) (void)hipHostFree(h);
-        if (d) (void)hipFree(d);
-        return fail(VX_ENOMEM, "vx_hybrid_submit: hybrid metadata allocation failed");
-    }
-    s.h_hy = h;
-    s.d_hy = d;
-    s.hy_joined = ev;
-    return 0;
-}
-
 void reset_fill(Slot& s) {
     s.tags.clear();
     s.runs.clear();
@@ -249,16 +202,12 @@ void reset_fill(Slot& s) {
     s.uniform = true;
     s.has_expected = false;
     s.use_table = false;
-    s.v2 = false;
-    s.v2_kmax = 0;
-    s.hybrid = false;
-    s.hy_total = 0;
-    s.hy_lanes.clear();
-    s.hy_rows.clear();
+    s.kind = Slot::Kind::V1;
+    s.v2.kmax = 0;
+    s.hy.total = 0;
+    s.hy.rows.clear();
     s.all_mapped = true;
 }
-
-int launch_slot_impl(vx_ctx* c, int si);
 
 // CPUs this process may run on (the container's or cgroup's share, not the
 // machine's: hardware_concurrency reports every CPU of a large host).
@@ -271,69 +220,8 @@ unsigned usable_cpus() {
     return std::max(1u, std::thread::hardware_concurrency());
 }
 
-// A host batch's unregistered pieces reach the pinned stage here, split by
-// bytes over up to 16 threads: one thread's memcpy (~10-13 GiB/s) bounded
-// config 3 from plain memory.  The caller's buffers stay
-// valid because vx_*_batch returns only after every slot has completed (or,
-// on an error, after every in-flight slot has been waited for: abandon_batch).
-// A thread that cannot be created leaves its range to the calling thread, so
-// no exception crosses the C ABI.
-void stage_copies(Slot& s) {
-    if (s.staged.empty()) return;
-    const uint64_t per = 16ull << 20;
-    static const unsigned hw = usable_cpus();
-    const unsigned T = (unsigned)std::min<uint64_t>({16, hw, std::max<uint64_t>(1, s.staged_bytes / per)});
-    auto copy = [&s](size_t a, size_t b) {
-        for (size_t k = a; k < b; ++k) std::memcpy(s.h_stage + s.staged[k].off, s.staged[k].src, s.staged[k].len);
-    };
-    if (T <= 1) {
-        copy(0, s.staged.size());
-    } else {
-        // contiguous ranges of roughly staged_bytes / T each
-        std::vector<size_t> cut{0};
-        uint64_t acc = 0, next = s.staged_bytes / T;
-        for (size_t k = 0; k < s.staged.size() && cut.size() < T; ++k) {
-            acc += s.staged[k].len;
-            if (acc >= next) {
-                cut.push_back(k + 1);
-                next += s.staged_bytes / T;
-            }
-        }
-        cut.push_back(s.staged.size());
-        std::vector<std::thread> th;
-        th.reserve(cut.size());
-        size_t t = 1;
-        try {
-            for (; t + 1 < cut.size(); ++t) th.emplace_back(copy, cut[t], cut[t + 1]);
-        } catch (...) {  // std::system_error (EAGAIN) or bad_alloc: copy the rest here
-        }
-        copy(cut[0], cut[1]);
-        for (size_t u = t; u + 1 < cut.size(); ++u) copy(cut[u], cut[u + 1]);
-        for (auto& x : th) x.join();
-    }
-    s.staged.clear();
-    s.staged_bytes = 0;
-}
-
-// Order slot si's H2D after the previously launched slot's (one PCIe stream
-// of copies across all slots): the host waits for the previous slot's copy,
-// with no cross-stream wait.  That keeps copies back to back with a gap of
-// one host wake-up and blocks the host for at most one batch's copy.  The
-// alternatives measured worse and were removed in round 4 (EXPERIMENTS.md):
-// a stream wait on the previous `copied` event blocked hipMemcpyAsync for
-// ~8-9 ms at a time and left PCIe idle (34-46 GiB/s, 38-40 with an extra
-// host wait two launches back), one dedicated copy stream 45, this 48.5-48.7
-// (8192 x 256 KiB through vx_verify_batch, profiles/r01/h2d_modes/).
-int chain_h2d(vx_ctx* c, int si) {
-    const int last = c->last_launched;
-    if (last >= 0 && last != si) VX_HIP(hipEventSynchronize(c->slots[last].copied));
-    return 0;
-}
-
-void mark_launched(vx_ctx* c, int si) { c->last_launched = si; }
-
 // Run every command type a batch uses once on every slot stream, in the
-// launch pattern of launch_slot_impl (cross-slot copy chain, large and small
+// launch pattern of vx_slots.hip's launch_v1 (cross-slot copy chain, large and small
 // H2D, both default kernels, D2H).  The HIP runtime sets up the hardware
 // queues and copy paths behind a stream on first use, and that blocked the
 // host for ~8 ms inside hipMemcpyAsync on the first two slots of the first
@@ -367,417 +255,6 @@ int warm_slots(vx_ctx* c) {
     }
     for (auto& s : c->slots) VX_HIP(hipStreamSynchronize(s.stream));
     c->last_launched = prev;
-    return 0;
-}
-
-// A failed launch leaves a slot half-enqueued: the context turns sticky and
-// every later call reports the error (vx_destroy still cleans up).
-int launch_slot(vx_ctx* c, int si) {
-#ifdef VX_TEST_HOOKS
-    if (c->fail_launch_after >= 0 && c->fail_launch_after-- == 0)
-        return c->sticky = fail(VX_EDEVICE, "launch: injected device failure (vx_tuning_fail_launch_after)");
-#endif
-    const int rc = launch_slot_impl(c, si);
-    if (rc) c->sticky = rc;
-    return rc;
-}
-
-// Every eligible slot goes zero-copy: the kernel beats gather + hash
-// everywhere measured (profiles/r03/zero_copy/).  Full async slots (round-3 A/B, alternating
-// runs of async_probe, one registered mmap per buffer): 16 KiB 33 -> 48
-// GiB/s, 256 / 512 KiB 47.8 -> 48.8 / 48.1 -> 49.0, 1 / 2 / 4 MiB 44 -> 48 /
-// 34 -> 44 / 30 -> 35.  Small, latency-bound batches (round-3 loop-latency A/B,
-// 32-piece batches) only in the three-wave form: download-loop p50 at 32 KiB
-// 0.68 ms against 0.70, 256 KiB 3.75 against 3.75, 2 MiB 26.6 against 27.7.
-
-// The loader wave takes the loads off the producer, so the chain reading host
-// memory runs at 0.78 us per block instead of 0.83-0.86 (tools/zc_chain_probe
-// .py): latency-bound batches then finish 7-9 % sooner (p50 at 256 KiB 3.75
-// ms against 4.13, 2 MiB 26.7 against 28.8).  On full slots, where PCIe
-// binds, it ran 2-4 % behind the pair (256 KiB streamed 49.1 against 50.9
-// GiB/s; ab_loader3.jsonl), so those keep the pair.
-bool zc_loader_wins(uint32_t n) { return n < kZcMinPieces; }
-
-int launch_slot_impl(vx_ctx* c, int si) {
-    Slot& s = c->slots[si];
-    if (c->filling == si) {
-        c->filling = -1;
-        c->flush_pending = false;
-    }
-    if (s.n == 0) {
-        s.state = Slot::FREE;
-        return 0;
-    }
-    if (s.hybrid) return launch_hybrid_slot(c, si);  // vx_hybrid.hip: never zero-copy, its own sequence
-    hipStream_t cs = s.stream;
-    // Zero-copy slot: every piece is read by the hash kernel itself, so no
-    // bytes cross PCIe ahead of it and nothing waits for the copy chain.
-    // Any slot qualifies, async or inside a host batch (vx_hash.h).
-    // A v2 slot never does: it has no chain for the transfer to hide behind,
-    // so gather-then-hash loses only the hash of one leaf.
-    const bool zc = s.gtiles && s.all_mapped && c->cfg.zero_copy && !s.v2;
-    stage_copies(s);
-    if (!zc)
-        if (int rc = chain_h2d(c, si)) return rc;
-    for (const DirectRun& r : s.druns)
-        VX_HIP(hipMemcpyAsync(s.d_arena + r.lo, r.host, r.hi - r.lo, hipMemcpyHostToDevice, cs));
-    for (const Run& r : s.runs)
-        VX_HIP(hipMemcpyAsync(s.d_arena + r.lo, s.h_stage + r.lo, r.hi - r.lo, hipMemcpyHostToDevice, cs));
-    const uint32_t n = s.n;
-    if (!zc && (!s.uniform || s.gtiles || s.v2)) {
-        VX_HIP(hipMemcpyAsync(s.d_offsets, s.h_offsets, (size_t)n * 8, hipMemcpyHostToDevice, cs));
-        VX_HIP(hipMemcpyAsync(s.d_lens, s.h_lens, (size_t)n * 4, hipMemcpyHostToDevice, cs));
-    }
-    if (zc) {
-        VX_HIP(hipMemcpyAsync(s.d_lens, s.h_lens, (size_t)n * 4, hipMemcpyHostToDevice, cs));
-        VX_HIP(hipMemcpyAsync(s.d_src, s.h_src, (size_t)n * 8, hipMemcpyHostToDevice, cs));
-    } else if (s.gtiles) {
-        VX_HIP(hipMemcpyAsync(s.d_src, s.h_src, (size_t)n * 8, hipMemcpyHostToDevice, cs));
-        VX_HIP(hipMemcpyAsync(s.d_tfirst, s.h_tfirst, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, cs));
-        // Slots of long pieces (>= 2 MiB on average) hash with a few
-        // chain-bound pairs that barely touch HBM, so the gather may use 128
-        // workgroups: async 2 / 4 MiB pieces 39.8 -> 43.2 / 35.8 -> 39.6 GiB/s.
-        // With shorter pieces the hash kernels compete and 128 cost up to 10 %
-        // (1 MiB: -2 %).
-        const uint32_t grid = s.bytes >= (uint64_t)n << 21 ? 128u : 0u;
-        hipError_t e = vx::launch_gather(s.d_src, s.d_offsets, s.d_lens, s.d_tfirst, n, s.gtiles, s.d_arena, cs, grid);
-        if (e != hipSuccess) return hip_fail(e, "gather launch");
-        c->stats.gather_tiles += s.gtiles;
-    }
-    if (s.v2) {
-        VX_HIP(hipMemcpyAsync(s.d_log2w, s.h_log2w, n, hipMemcpyHostToDevice, cs));
-        if (s.has_expected) VX_HIP(hipMemcpyAsync(s.d_exp32, s.h_exp32, (size_t)n * 32, hipMemcpyHostToDevice, cs));
-    } else if (s.use_table)
-        VX_HIP(hipMemcpyAsync(s.d_pidx, s.h_pidx, (size_t)n * 4, hipMemcpyHostToDevice, cs));
-    else if (s.has_expected)
-        VX_HIP(hipMemcpyAsync(s.d_expected, s.h_expected, (size_t)n * 20, hipMemcpyHostToDevice, cs));
-    const uint8_t* d_exp = s.use_table ? c->d_table : (s.has_expected ? s.d_expected : nullptr);
-    const uint32_t* d_row = s.use_table ? s.d_pidx : nullptr;
-    VX_HIP(hipEventRecord(s.copied, cs));
-    mark_launched(c, si);
-    hipError_t e;
-    if (s.v2) {
-        // The fused piece kernel at the slot's widest tree; above 256 leaves
-        // it leaves tile tops in d_tops and the node kernel follows
-        // (launch_merkle_pieces).
-        const uint32_t K = s.v2_kmax;
-#if VX_MERKLE_ASYNC_FUSED
-        const uint64_t need = K > 8 ? ((uint64_t)n << (K - 8)) * 32 + n : 0;
-#else
-        const uint64_t need = ((uint64_t)n << K) * 32;  // the A/B leg (vx_tuning.h): the leaf + node pair's leaf array
-#endif
-        if (need > s.tops_cap) {
-            if (s.d_tops) (void)hipFree(s.d_tops);
-            s.d_tops = nullptr;
-            s.tops_cap = 0;
-            if (hipMalloc(&s.d_tops, need) != hipSuccess) return fail(VX_ENOMEM, "v2 tile tops allocation failed");
-            s.tops_cap = need;
-        }
-#if VX_MERKLE_ASYNC_FUSED
-        e = vx::launch_merkle_pieces(s.d_arena, s.d_offsets, s.d_lens, s.d_log2w, n, K, s.d_tops, s.d_roots,
-                                     s.has_expected ? s.d_exp32 : nullptr, s.has_expected ? s.d_matched : nullptr,
-                                     s.stream);
-#else
-        e = vx::launch_merkle_ragged(s.d_arena, s.d_offsets, s.d_lens, s.d_log2w, n, K, s.d_tops, s.d_roots,
-                                     s.has_expected ? s.d_exp32 : nullptr, s.has_expected ? s.d_matched : nullptr,
-                                     s.stream);
-#endif
-        if (e != hipSuccess) return hip_fail(e, "merkle piece kernel launch");
-        VX_HIP(hipMemcpyAsync(s.h_roots, s.d_roots, (size_t)n * 32, hipMemcpyDeviceToHost, s.stream));
-    } else if (zc) {
-        const bool loader = zc_loader_wins(n);
-        e = vx::launch_zero_copy(s.d_src, s.d_lens, n, s.d_digests, d_exp, s.d_matched, loader, s.stream, d_row);
-        c->stats.zero_copy_slots++;
-        c->stats.zero_copy_loader_slots += loader;
-    } else if (s.uniform) {
-        const uint32_t len = s.h_lens[0];
-        const uint64_t stride = align_up(std::max<uint32_t>(len, 1), kAlign);
-        e = vx::launch_uniform(s.d_arena, stride, len, n, s.d_digests, d_exp, s.d_matched, s.stream,
-                               vx::kUniformDefault, d_row);
-    } else {
-        uint64_t max_len = 0, total = 0;
-        for (uint32_t i = 0; i < n; ++i) {
-            max_len = std::max<uint64_t>(max_len, s.h_lens[i]);
-            total += s.h_lens[i];
-        }
-        e = vx::launch_ragged(s.d_arena, s.d_offsets, s.d_lens, nullptr, n, s.d_digests, d_exp, s.d_matched,
-                              s.stream, vx::plan_ragged(n, max_len, total), d_row);
-    }
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    if (!s.v2) VX_HIP(hipMemcpyAsync(s.h_digests, s.d_digests, (size_t)n * 20, hipMemcpyDeviceToHost, s.stream));
-    if (s.has_expected)
-        VX_HIP(hipMemcpyAsync(s.h_matched, s.d_matched, n, hipMemcpyDeviceToHost, s.stream));
-    VX_HIP(hipEventRecord(s.done, s.stream));
-    s.state = Slot::INFLIGHT;
-    s.seq = c->seq++;
-    c->stats.batches++;
-    return 0;
-}
-
-// Batch latency: first piece queued -> results harvested, into the log2
-// histogram of vx_stats.
-void record_batch_latency(vx_ctx* c, std::chrono::steady_clock::time_point t_open) {
-    const auto us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_open);
-    const uint64_t v = (uint64_t)std::max<int64_t>(0, us.count());
-    vx_stats& st = c->stats;
-    st.batch_latency_count++;
-    st.batch_latency_sum_us += v;
-    st.batch_latency_max_us = std::max(st.batch_latency_max_us, v);
-    int k = 0;
-    while (k + 1 < VX_STATS_HIST && (v >> (k + 1)) != 0) ++k;
-    st.batch_latency_hist[k]++;
-}
-
-void harvest(vx_ctx* c, Slot& s) {
-    uint64_t bytes = 0, bad = 0;
-    for (uint32_t i = 0; i < s.n; ++i) {
-        const uint8_t matched = s.has_expected ? s.h_matched[i] : 0;
-        if (s.hybrid) {
-            vx_hybrid_completion r{};
-            r.tag = s.tags[i];
-            r.matched = matched;
-            std::memcpy(r.sha1, s.h_digests + (size_t)i * 20, 20);
-            std::memcpy(r.root, s.h_roots + (size_t)i * 32, 32);
-            c->done_hy.push_back(r);
-            bytes += s.h_lens[i];
-            bad += (s.hy_lanes[i].flags & ~matched) != 0;  // once, when any compared side fails
-            continue;
-        }
-        if (s.v2) {
-            vx_merkle_completion r{};
-            r.tag = s.tags[i];
-            r.matched = matched;
-            std::memcpy(r.root, s.h_roots + (size_t)i * 32, 32);
-            c->done_v2.push_back(r);
-        } else {
-            vx_completion r{};
-            r.tag = s.tags[i];
-            r.matched = matched;
-            std::memcpy(r.digest, s.h_digests + (size_t)i * 20, 20);
-            c->done.push_back(r);
-        }
-        bytes += s.h_lens[i];
-        bad += s.has_expected && !matched;
-    }
-    if (s.n) {
-        c->stats.pieces_completed += s.n;
-        if (c->harvest_counts_mismatches) c->stats.pieces_mismatched += bad;
-        c->stats.bytes_completed += bytes;
-        record_batch_latency(c, s.t_open);
-    }
-    reset_fill(s);
-    s.state = Slot::FREE;
-}
-
-// Harvest finished slots (oldest first).  block=true waits for the oldest.
-int reap(vx_ctx* c, bool block_oldest) {
-    std::vector<int> order;
-    for (int i = 0; i < (int)c->slots.size(); ++i)
-        if (c->slots[i].state == Slot::INFLIGHT) order.push_back(i);
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return c->slots[a].seq < c->slots[b].seq; });
-    bool first = true;
-    for (int i : order) {
-        Slot& s = c->slots[i];
-        hipError_t q = (block_oldest && first) ? hipEventSynchronize(s.done) : hipEventQuery(s.done);
-        first = false;
-        if (q == hipSuccess) {
-            harvest(c, s);
-        } else if (q != hipErrorNotReady) {
-            c->sticky = hip_fail(q, "batch failed on device");
-            return c->sticky;
-        }
-    }
-    return 0;
-}
-
-// A flush may launch now if, after it, a slot is still free to fill (with a
-// single slot: if nothing is in flight).
-bool may_launch_now(const vx_ctx* c) {
-    int inflight = 0;
-    for (const Slot& s : c->slots) inflight += s.state == Slot::INFLIGHT;
-    return inflight < std::max(1, (int)c->slots.size() - 1);
-}
-
-// may_wait = false (an async submit with refuse_when_full): harvest what has
-// finished without blocking, and if no slot is free then, VX_EBUSY.
-int acquire_filling(vx_ctx* c, bool may_wait = true) {
-    if (c->filling >= 0) return c->filling;
-    for (int attempt = 0;; ++attempt) {
-        for (int i = 0; i < (int)c->slots.size(); ++i) {
-            if (c->slots[i].state == Slot::FREE) {
-                reset_fill(c->slots[i]);
-                c->slots[i].state = Slot::FILLING;
-                c->filling = i;
-                return i;
-            }
-        }
-        if (!may_wait) {
-            if (attempt > 0) {
-                c->stats.submits_refused++;
-                return fail(VX_EBUSY, "vx_submit: every slot in flight (refuse_when_full)");
-            }
-            if (int rc = reap(c, /*block_oldest=*/false)) return rc;
-            continue;
-        }
-        const auto t0 = std::chrono::steady_clock::now();
-        int rc = reap(c, /*block_oldest=*/true);
-        c->stats.submit_stall_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
-                                        std::chrono::steady_clock::now() - t0).count();
-        if (rc) return rc;
-    }
-}
-
-// piece_row < 0: compare with `expected` (may be NULL); piece_row >= 0:
-// compare with row piece_row of the device piece table.
-// v2_log2w >= 0: a v2 piece (vx_merkle_submit) of 2^v2_log2w leaf slots,
-// `expected` its 32-byte root; placement, ownership and errors are the same.
-// hy: a hybrid piece (vx_hybrid_submit) of hy->pad_len implied zeros and 2^hy->log2w
-// leaf slots, `expected` its SHA-1 row and hy->exp_root its root (piece_row >= 0:
-// row piece_row of the two hybrid tables).
-int submit_impl(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, const uint8_t* expected,
-                int64_t piece_row, int v2_log2w, const HybridPiece* hy) {
-    if (c->sticky) return c->sticky;
-    if (!data && len) return fail(VX_EINVAL, "vx_submit: data is NULL");
-    if (len > c->cfg.max_piece_len) return fail(VX_ERANGE, "vx_submit: piece longer than max_piece_len");
-#ifdef VX_TEST_HOOKS
-    if (c->fail_submit_after >= 0 && c->fail_submit_after-- == 0)
-        return fail(VX_ENOMEM, "vx_submit: injected failure (vx_tuning_fail_submit_after)");
-#endif
-    const bool table = piece_row >= 0;
-    const bool v2 = v2_log2w >= 0;
-    const bool hybrid = hy != nullptr;
-    const uint32_t tree_log2w = hybrid ? hy->log2w : (uint32_t)std::max(v2_log2w, 0);
-    const uint64_t hy_total = hybrid && hy->pad_len ? (uint64_t)len + hy->pad_len : 0;
-    const bool may_wait = !c->cfg.refuse_when_full || c->bulk;  // host batches always wait
-    int si = acquire_filling(c, may_wait);
-    if (si < 0) return si;
-    Slot* s = &c->slots[si];
-    uint64_t off = align_up(s->bytes, kAlign);
-    // the piece kernel runs (pieces << widest log2w) lanes, a 32-bit count
-    const bool v2_lanes_full =
-        (v2 || hybrid) && ((uint64_t)(s->n + 1) << std::max<uint32_t>(s->v2_kmax, tree_log2w)) > (1ull << 31);
-    // a slot holds either table-indexed or explicit-digest pieces, and one kind: v1, v2 or hybrid;
-    // a hybrid slot's padded pieces have one total length (the finish kernel's final block)
-    const bool other_total = hy_total && s->hy_total && s->hy_total != hy_total;
-    if (s->n == s->cap || off + len > s->arena_cap ||
-        (s->n && (s->use_table != table || s->v2 != v2 || s->hybrid != hybrid || other_total)) ||
-        (s->n && v2_lanes_full)) {
-        int rc = launch_slot(c, si);
-        if (rc) return rc;
-        si = acquire_filling(c, may_wait);
-        if (si < 0) return si;
-        s = &c->slots[si];
-        off = 0;
-    }
-    const uint32_t i = s->n;
-    const uint8_t* dev = nullptr;
-    if (v2)
-        if (int rc = ensure_v2(*s)) return rc;
-    if (hybrid)
-        if (int rc = ensure_hybrid(*s)) return rc;
-    s->h_src[i] = 0;
-    if (i == 0) s->t_open = std::chrono::steady_clock::now();
-    if (len && (reinterpret_cast<uintptr_t>(data) & 15) == 0 && is_registered(c, data, len, &dev)) {
-        // Registered, 16-byte aligned: the launch's gather kernel pulls it
-        // through the range's device mapping.
-        s->h_src[i] = reinterpret_cast<uint64_t>(dev);
-        s->gtiles += vx::gather_tiles(len);
-    } else if (len) {
-        // all_mapped is cleared below, once the piece is certainly queued: a
-        // refused piece (VX_ENOMEM from ensure_stage) must not take the rest
-        // of the slot off the zero-copy path.
-        if (is_registered(c, data, len)) {
-            // Pinned source: DMA straight from the caller's buffer at launch;
-            // pieces adjacent in host memory AND in the arena share one copy.
-            if (!s->druns.empty() && s->druns.back().hi == off &&
-                s->druns.back().host + (s->druns.back().hi - s->druns.back().lo) == data)
-                s->druns.back().hi = off + len;
-            else
-                s->druns.push_back(DirectRun{data, off, off + len});
-        } else {
-            if (int rc = ensure_stage(c, *s)) return rc;
-            c->stats.staged_bytes += len;
-            if (c->bulk) {  // a host batch: copied in parallel at launch (stage_copies)
-                s->staged.push_back(StageCopy{data, off, len});
-                s->staged_bytes += len;
-            } else {
-                std::memcpy(s->h_stage + off, data, len);
-            }
-            if (!s->runs.empty() && s->runs.back().hi == off)
-                s->runs.back().hi = off + len;
-            else if (!s->runs.empty() && align_up(s->runs.back().hi, kAlign) == off)
-                s->runs.back().hi = off + len;  // alignment gap travels too
-            else
-                s->runs.push_back(Run{off, off + len});
-        }
-        s->all_mapped = false;
-    }
-    s->h_offsets[i] = off;
-    s->h_lens[i] = len;
-    s->h_tfirst[i + 1] = s->gtiles;
-    // Equal lengths at 256-byte aligned back-to-back offsets are a uniform
-    // batch: offset(i) = i * align_up(len, 256) (the uniform kernel's layout).
-    if (i > 0 && len != s->h_lens[0]) s->uniform = false;
-    // a v2 piece's expected row is its 32-byte root, in the slot's v2 block
-    const size_t dlen = v2 ? 32 : 20;
-    uint8_t* h_exp = v2 ? s->h_exp32 : s->h_expected;
-    if (v2) {
-        s->v2 = true;
-        s->h_log2w[i] = (uint8_t)v2_log2w;
-        s->v2_kmax = std::max<uint32_t>(s->v2_kmax, (uint32_t)v2_log2w);
-    }
-    if (hybrid) {
-        // The verdict column always comes back; which sides were given is the
-        // lane's flags, so a side's bit is exact and not "compared with a zero row".
-        Slot::HybridRows rows{};
-        if (expected) std::memcpy(rows.sha1, expected, VX_DIGEST_LEN);
-        if (hy->exp_root) std::memcpy(rows.root, hy->exp_root, VX_SHA256_LEN);
-        rows.log2w = (uint8_t)hy->log2w;
-        const uint8_t flags = table ? 3 : (uint8_t)((expected ? 1 : 0) | (hy->exp_root ? 2 : 0));
-        s->hy_rows.push_back(rows);
-        s->hy_lanes.push_back(vx_hybrid_slot::lane(off, len, hy->pad_len, flags));
-        s->hybrid = true;
-        s->v2_kmax = std::max<uint32_t>(s->v2_kmax, hy->log2w);
-        if (hy_total) s->hy_total = hy_total;
-        s->h_pidx[i] = table ? (uint32_t)piece_row : i;
-        s->use_table = table;
-        s->has_expected = true;
-    } else if (table) {
-        s->h_pidx[i] = (uint32_t)piece_row;
-        s->use_table = true;
-        s->has_expected = true;
-    } else if (expected) {
-        std::memcpy(h_exp + (size_t)i * dlen, expected, dlen);
-        if (i > 0 && !s->has_expected) {
-            // earlier pieces of this batch had no expected digest: they get
-            // matched = 0 against a zero table, which nobody reads.
-            std::memset(h_exp, 0, (size_t)i * dlen);
-        }
-        s->has_expected = true;
-    } else if (s->has_expected) {
-        std::memset(h_exp + (size_t)i * dlen, 0, dlen);
-    }
-    s->tags.push_back(tag);
-    s->n = i + 1;
-    s->bytes = off + std::max<uint32_t>(len, 1);
-    c->pending++;
-    if (s->n >= c->cfg.batch_pieces && !c->bulk) {
-        if (int rc = launch_slot(c, si)) {
-            // One rule for every submit (vx_hash.h): a non-zero return means
-            // the piece was NOT taken.  The launch failed (the context is now
-            // sticky), so this piece leaves the batch again and goes back to
-            // the caller with the error; the rest of the slot stays pending and
-            // is what the caller recovers after vx_poll reports the failure.
-            s->tags.pop_back();
-            if (hybrid) {
-                s->hy_lanes.pop_back();
-                s->hy_rows.pop_back();
-            }
-            s->n = i;
-            c->pending--;
-            return rc;
-        }
-    }
     return 0;
 }
 
@@ -995,42 +472,15 @@ int begin_bulk_call(vx_ctx* c, const std::string& who, bool need_idle) {
 // is dropped: the filling slot is discarded without its deferred stage
 // copies, completions already queued are cleared, and pending returns to 0
 // (batch_impl starts with nothing pending), so later batches, vx_poll and
-// vx_unregister_host_buffer see a clean context.
-void abandon_batch(vx_ctx* c) {
+// vx_unregister_host_buffer see a clean context.  Only c->done: a bulk call
+// submits v1 pieces alone, so the v2 and hybrid queues hold nothing of it.
+static void abandon_batch(vx_ctx* c) {
     wait_and_free_inflight(c);
     release_filling_slots(c);
     c->done.clear();
     c->filling = -1;
     c->flush_pending = false;
     c->pending = 0;
-}
-
-// vx_poll / vx_merkle_poll: harvest what has finished (slots of either kind),
-// then hand out the caller's kind from its own queue.
-template <class Completion>
-int64_t poll_impl(vx_ctx* c, std::deque<Completion>& done, Completion* out, size_t max) {
-    int rc = set_device(c);
-    if (rc) return rc;
-    if (c->sticky) {
-        // Failed context: hand out every result the device did produce (batches
-        // that finished, harvested now or earlier), then the error.  The tags
-        // never returned are the pieces to re-hash elsewhere.
-        const int sticky = c->sticky;
-        (void)reap(c, false);
-        c->sticky = sticky;
-        if (done.empty()) return sticky;
-    } else {
-        rc = reap(c, false);
-        if (rc) return rc;
-        if (c->flush_pending && c->filling >= 0 && may_launch_now(c) && (rc = launch_slot(c, c->filling))) return rc;
-    }
-    size_t k = 0;
-    while (k < max && !done.empty()) {
-        out[k++] = done.front();
-        done.pop_front();
-    }
-    c->pending -= k;
-    return (int64_t)k;
 }
 
 }  // namespace vxe
@@ -1202,161 +652,6 @@ int vx_unregister_host_buffer(vx_ctx* c, void* ptr) {
     return 0;
 }
 
-int vx_submit(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, const uint8_t* expected) {
-    if (!c) return fail(VX_EINVAL, "vx_submit: NULL context");
-    int rc = set_device(c);
-    if (rc) return rc;
-    return submit_impl(c, tag, data, len, expected);
-}
-
-int vx_set_piece_table(vx_ctx* c, const uint8_t* table, uint32_t n_pieces) {
-    if (!c || (n_pieces && !table)) return fail(VX_EINVAL, "vx_set_piece_table: bad argument");
-    if (c->pending || c->filling >= 0) return fail(VX_EBUSY, "vx_set_piece_table: pieces in flight");
-    int rc = set_device(c);
-    if (rc) return rc;
-    if (c->d_table) (void)hipFree(c->d_table);
-    c->d_table = nullptr;
-    c->n_table = 0;
-    if (!n_pieces) return 0;
-    if (hipMalloc(&c->d_table, (size_t)n_pieces * 20) != hipSuccess)
-        return fail(VX_ENOMEM, "vx_set_piece_table: device allocation failed");
-    VX_HIP(hipMemcpy(c->d_table, table, (size_t)n_pieces * 20, hipMemcpyHostToDevice));
-    c->n_table = n_pieces;
-    return 0;
-}
-
-int vx_submit_piece(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, uint32_t piece_index) {
-    if (!c) return fail(VX_EINVAL, "vx_submit_piece: NULL context");
-    if (piece_index >= c->n_table) return fail(VX_EINVAL, "vx_submit_piece: piece_index outside the piece table");
-    int rc = set_device(c);
-    if (rc) return rc;
-    return submit_impl(c, tag, data, len, nullptr, (int64_t)piece_index);
-}
-
-// Launch the filling slot unless that would leave no slot free for the next
-// submit: then the slot stays open and keeps collecting pieces, and vx_poll
-// launches it as soon as a batch completes.  So under load batches grow
-// instead of the event-loop thread blocking in vx_submit for a whole batch
-// (DESIGN.md §6.5).
-int vx_flush(vx_ctx* c) {
-    if (!c) return fail(VX_EINVAL, "vx_flush: NULL context");
-    if (c->sticky) return c->sticky;
-    if (c->filling < 0 || c->slots[c->filling].n == 0) return 0;
-    int rc = set_device(c);
-    if (rc) return rc;
-    if ((rc = reap(c, false))) return rc;
-    if (!may_launch_now(c)) {
-        c->flush_pending = true;
-        return 0;
-    }
-    return launch_slot(c, c->filling);
-}
-
-int64_t vx_poll(vx_ctx* c, vx_completion* out, size_t max) {
-    if (!c || (!out && max)) return fail(VX_EINVAL, "vx_poll: bad argument");
-    return poll_impl(c, c->done, out, max);
-}
-
-int64_t vx_merkle_poll(vx_ctx* c, vx_merkle_completion* out, size_t max) {
-    if (!c || (!out && max)) return fail(VX_EINVAL, "vx_merkle_poll: bad argument");
-    return poll_impl(c, c->done_v2, out, max);
-}
-
-int vx_merkle_submit(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, uint32_t log2w,
-                     const uint8_t* expected) {
-    if (!c) return fail(VX_EINVAL, "vx_merkle_submit: NULL context");
-    if (len > c->cfg.max_piece_len) return fail(VX_ERANGE, "vx_merkle_submit: piece longer than max_piece_len");
-    if (log2w > VX_MERKLE_MAX_LOG2_WIDTH) return fail(VX_EINVAL, "vx_merkle_submit: log2w > 17");
-    if (len > (uint64_t)VX_MERKLE_BLOCK << log2w)
-        return fail(VX_EINVAL, "vx_merkle_submit: piece longer than its tree (16384 << log2w)");
-    uint64_t widest = VX_MERKLE_BLOCK;  // max_piece_len rounded up to a power of two
-    while (widest < c->cfg.max_piece_len) widest <<= 1;
-    if (((uint64_t)VX_MERKLE_BLOCK << log2w) > widest)
-        return fail(VX_EINVAL, "vx_merkle_submit: tree wider than max_piece_len");
-    int rc = set_device(c);
-    if (rc) return rc;
-    return submit_impl(c, tag, data, len, expected, -1, (int)log2w);
-}
-
-int64_t vx_hybrid_poll(vx_ctx* c, vx_hybrid_completion* out, size_t max) {
-    if (!c || (!out && max)) return fail(VX_EINVAL, "vx_hybrid_poll: bad argument");
-    return poll_impl(c, c->done_hy, out, max);
-}
-
-static int hybrid_submit(vx_ctx* c, const char* who, uint64_t tag, const uint8_t* data, uint32_t len, uint32_t pad_len,
-                         uint32_t log2w, const uint8_t* exp_sha1, const uint8_t* exp_root, int64_t row) {
-    const char* why = nullptr;
-    if (int rc = vx_hybrid_slot::check(len, pad_len, log2w, c->cfg.max_piece_len, &why))
-        return fail(rc, std::string(who) + ": " + why);
-    int rc = set_device(c);
-    if (rc) return rc;
-    const HybridPiece hy{pad_len, log2w, exp_root};
-    return submit_impl(c, tag, data, len, exp_sha1, row, -1, &hy);
-}
-
-int vx_hybrid_submit(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, uint32_t pad_len, uint32_t log2w,
-                     const uint8_t* exp_sha1, const uint8_t* exp_root) {
-    if (!c) return fail(VX_EINVAL, "vx_hybrid_submit: NULL context");
-    return hybrid_submit(c, "vx_hybrid_submit", tag, data, len, pad_len, log2w, exp_sha1, exp_root, -1);
-}
-
-int vx_hybrid_submit_piece(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, uint32_t pad_len,
-                           uint32_t log2w, uint32_t piece_index) {
-    if (!c) return fail(VX_EINVAL, "vx_hybrid_submit_piece: NULL context");
-    if (piece_index >= c->n_hy_table)
-        return fail(VX_EINVAL, "vx_hybrid_submit_piece: piece_index outside the hybrid piece tables");
-    return hybrid_submit(c, "vx_hybrid_submit_piece", tag, data, len, pad_len, log2w, nullptr, nullptr,
-                         (int64_t)piece_index);
-}
-
-int vx_hybrid_set_piece_tables(vx_ctx* c, const uint8_t* sha1_table, const uint8_t* roots_table, uint32_t n_pieces) {
-    if (!c || (n_pieces && (!sha1_table || !roots_table)))
-        return fail(VX_EINVAL, "vx_hybrid_set_piece_tables: bad argument");
-    if (c->pending || c->filling >= 0) return fail(VX_EBUSY, "vx_hybrid_set_piece_tables: pieces in flight");
-    int rc = set_device(c);
-    if (rc) return rc;
-    if (c->d_hy_sha1) (void)hipFree(c->d_hy_sha1);
-    if (c->d_hy_roots) (void)hipFree(c->d_hy_roots);
-    c->d_hy_sha1 = c->d_hy_roots = nullptr;
-    c->n_hy_table = 0;
-    if (!n_pieces) return 0;
-    if (hipMalloc(&c->d_hy_sha1, (size_t)n_pieces * 20) != hipSuccess ||
-        hipMalloc(&c->d_hy_roots, (size_t)n_pieces * 32) != hipSuccess) {
-        if (c->d_hy_sha1) (void)hipFree(c->d_hy_sha1);
-        c->d_hy_sha1 = c->d_hy_roots = nullptr;
-        return fail(VX_ENOMEM, "vx_hybrid_set_piece_tables: device allocation failed");
-    }
-    VX_HIP(hipMemcpy(c->d_hy_sha1, sha1_table, (size_t)n_pieces * 20, hipMemcpyHostToDevice));
-    VX_HIP(hipMemcpy(c->d_hy_roots, roots_table, (size_t)n_pieces * 32, hipMemcpyHostToDevice));
-    c->n_hy_table = n_pieces;
-    return 0;
-}
-
-int vx_drain(vx_ctx* c, uint32_t timeout_ms) {
-    if (!c) return fail(VX_EINVAL, "vx_drain: NULL context");
-    if (c->sticky) return c->sticky;
-    int rc = set_device(c);
-    if (rc) return rc;
-    if (c->filling >= 0 && (rc = launch_slot(c, c->filling))) return rc;  // forced, unlike vx_flush
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-        bool any = false;
-        for (auto& s : c->slots) any |= s.state == Slot::INFLIGHT;
-        if (!any) return 0;
-        if (timeout_ms == 0) {
-            rc = reap(c, true);
-        } else {
-            rc = reap(c, false);
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(timeout_ms))
-                return fail(VX_EBUSY, "vx_drain: timeout");
-            std::this_thread::sleep_for(std::chrono::microseconds(100));
-        }
-        if (rc) return rc;
-    }
-}
-
-uint64_t vx_pending(const vx_ctx* c) { return c ? c->pending : 0; }
-
 static int batch_impl(vx_ctx* c, const uint8_t* const* ptrs, const uint32_t* lens, const uint8_t* expected, size_t n,
                       uint8_t* matched_out, uint8_t* digests_out) {
     if (!c) return fail(VX_EINVAL, "batch: NULL context");
@@ -1405,7 +700,8 @@ static int batch_impl(vx_ctx* c, const uint8_t* const* ptrs, const uint32_t* len
     c->bulk = true;
     for (size_t p = 0; p < n; ++p) {
         const size_t i = order[p];
-        rc = submit_impl(c, i, ptrs[i], lens[i], expected ? expected + i * 20 : nullptr);
+        rc = submit_impl(c, {.kind = Slot::Kind::V1, .tag = i, .data = ptrs[i], .len = lens[i],
+                             .expected = expected ? expected + i * 20 : nullptr});
         if (!rc && c->done.size() >= 65536) rc = collect();
         if (rc) break;
     }

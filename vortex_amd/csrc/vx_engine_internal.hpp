@@ -1,6 +1,7 @@
 // vx_engine_internal.hpp — what every host unit of the engine shares (DESIGN.md
 // "Host engine"): error reporting, the slot and context structs (one layout
-// with and without VX_TEST_HOOKS), the slot primitives of vx_engine.hip.
+// with and without VX_TEST_HOOKS), and the functions that cross units: the
+// context's primitives (vx_engine.hip) and the slot path's (vx_slots.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -98,37 +99,38 @@ struct Slot {
     uint8_t* d_expected = nullptr;
     uint8_t* d_digests = nullptr;
     uint8_t* d_matched = nullptr;
-    // v2 pieces (vx_merkle_submit), allocated on the slot's first v2 use
-    // (ensure_v2): a pinned and a device block of expected roots (32 cap) |
-    // roots (32 cap) | log2w (cap); the verdicts share h_matched / d_matched.
-    uint8_t* h_v2 = nullptr;
-    uint8_t* d_v2 = nullptr;
-    uint8_t* h_exp32 = nullptr;
-    uint8_t* h_roots = nullptr;
-    uint8_t* h_log2w = nullptr;
-    uint8_t* d_exp32 = nullptr;
-    uint8_t* d_roots = nullptr;
-    uint8_t* d_log2w = nullptr;
-    // the piece kernel's work area for trees wider than 256 leaves (tile tops |
-    // their log2w), grown when a launch needs more
-    uint8_t* d_tops = nullptr;
-    uint64_t tops_cap = 0;
-    // hybrid pieces (vx_hybrid_submit), allocated on the slot's first hybrid
-    // use (ensure_hybrid): one pinned and one device block that hold a launch's
-    // whole metadata (vx_hybrid_slot::Pack; the SHA-1 states behind it on the
-    // device), and the event that joins the merkle side stream.  The roots land
-    // in the v2 block.  hy_lanes / hy_rows: what the submits filled in, packed
-    // at launch.
-    uint8_t* h_hy = nullptr;
-    uint8_t* d_hy = nullptr;
-    hipEvent_t hy_joined = nullptr;
-    struct HybridRows {
-        uint8_t sha1[VX_DIGEST_LEN], root[VX_SHA256_LEN], log2w;
-    };
-    std::vector<vx_hybrid_slot::Lane> hy_lanes;
-    std::vector<HybridRows> hy_rows;
-    bool hybrid = false;    // the slot's pieces are hybrid: a slot holds one kind
-    uint64_t hy_total = 0;  // ... and one padded total (len + pad_len of its padded pieces; 0: none yet)
+    // What the slot's pieces are (vx_submit / vx_merkle_submit / vx_hybrid_submit):
+    // a slot holds one kind.  A slot filled by hand after reset_fill (the file
+    // re-verify) is a v1 slot.
+    enum class Kind : uint8_t { V1, V2, Hybrid };
+    // v2 pieces, allocated on the slot's first v2 or hybrid use (ensure_v2): a
+    // pinned block h and a device block d of expected roots (32 cap) | roots
+    // (32 cap) | log2w (cap); the verdicts share h_matched / d_matched.
+    struct V2 {
+        uint8_t *h = nullptr, *d = nullptr;
+        uint8_t *h_exp32 = nullptr, *h_roots = nullptr, *h_log2w = nullptr;
+        uint8_t *d_exp32 = nullptr, *d_roots = nullptr, *d_log2w = nullptr;
+        // the piece kernel's work area for trees wider than 256 leaves (tile
+        // tops | their log2w), grown when a launch needs more
+        uint8_t* d_tops = nullptr;
+        uint64_t tops_cap = 0;
+        uint32_t kmax = 0;  // the widest log2w of the slot's v2 or hybrid pieces: the piece kernel runs n << kmax lanes
+    } v2;
+    // hybrid pieces, allocated on the slot's first hybrid use (ensure_hybrid):
+    // one pinned and one device block that hold a launch's whole metadata
+    // (vx_hybrid_slot::Pack; the SHA-1 states behind it on the device), and the
+    // event that joins the merkle side stream.  The roots land in the v2 block.
+    // rows: what the submits filled in per piece, packed at launch.
+    struct Hybrid {
+        uint8_t *h = nullptr, *d = nullptr;
+        hipEvent_t joined = nullptr;
+        struct Row {
+            vx_hybrid_slot::Lane lane;
+            uint8_t sha1[VX_DIGEST_LEN], root[VX_SHA256_LEN], log2w;
+        };
+        std::vector<Row> rows;
+        uint64_t total = 0;  // the one padded total (len + pad_len) of the slot's padded pieces; 0: none yet
+    } hy;
     std::vector<uint64_t> tags;
     std::vector<Run> runs;
     std::vector<DirectRun> druns;
@@ -138,9 +140,8 @@ struct Slot {
     uint64_t bytes = 0;
     bool uniform = true;
     bool has_expected = false;
-    bool use_table = false;  // expected digests come from the device piece table
-    bool v2 = false;         // the slot's pieces are v2 (vx_merkle_submit): a slot holds one kind
-    uint32_t v2_kmax = 0;    // ... and their widest log2w: the piece kernel runs n << v2_kmax lanes
+    bool use_table = false;  // expected rows come from the device piece table(s), row h_pidx[i]
+    Kind kind = Kind::V1;
     bool all_mapped = true;  // every non-empty piece is registered and 16-byte aligned (zero-copy candidate)
     enum State { FREE, FILLING, INFLIGHT } state = FREE;
     uint64_t seq = 0;
@@ -322,25 +323,32 @@ namespace vxe {
 // split's cold-start guesses before it has measured its own.
 constexpr double kChainBlock = 0.76e-6, kPcieRate = 52.0 * (1ull << 30);
 
-// Slot primitives (vx_engine.hip).
+// The context's primitives (vx_engine.hip).
 int set_device(const vx_ctx* c);
 bool is_registered(const vx_ctx* c, const void* p, size_t len, const uint8_t** dev = nullptr);
 unsigned usable_cpus();
 int ensure_stage(const vx_ctx* c, Slot& s);
 void reset_fill(Slot& s);
+// The slot path (vx_slots.hip).
 int chain_h2d(vx_ctx* c, int si);
 void mark_launched(vx_ctx* c, int si);
 int launch_slot(vx_ctx* c, int si);
 int reap(vx_ctx* c, bool block_oldest);
-// hy != nullptr: a hybrid piece (vx_hybrid_submit); `expected` is then its SHA-1 row.
-struct HybridPiece {
-    uint32_t pad_len, log2w;
-    const uint8_t* exp_root;
+bool zc_loader_wins(uint32_t n);
+// What one submit brings.  expected: the row to compare with, or NULL for none
+// (v1: a SHA-1 digest, v2: a root, hybrid: the SHA-1 row, exp_root its root);
+// table: compare with row `row` of the device piece table(s) instead.
+struct Piece {
+    Slot::Kind kind;
+    uint64_t tag;
+    const uint8_t* data;
+    uint32_t len;
+    bool table = false;
+    uint32_t row = 0;  // ... of the v1 table, or of the two hybrid tables
+    const uint8_t *expected = nullptr, *exp_root = nullptr;
+    uint32_t log2w = 0, pad_len = 0;  // v2 and hybrid: 2^log2w leaf slots; hybrid: implied zeros behind the data
 };
-int submit_impl(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, const uint8_t* expected,
-                int64_t piece_row = -1, int v2_log2w = -1, const HybridPiece* hy = nullptr);
-int launch_hybrid_slot(vx_ctx* c, int si);  // vx_hybrid.hip: launch_slot_impl's branch for a hybrid slot
-void abandon_batch(vx_ctx* c);
+int submit_impl(vx_ctx* c, const Piece& p);
 void release_filling_slots(vx_ctx* c);   // every FILLING slot (reserved, never launched) back to FREE
 void wait_and_free_inflight(vx_ctx* c);  // wait for every INFLIGHT slot, then free them unharvested
 // A bulk call's guard: nothing pending (VX_EBUSY), not sticky, an empty filling

@@ -1,21 +1,14 @@
 // vx_hybrid.hip — the hybrid (BEP 52 "upgrade path", v1 + v2) entries of
 // vx_hash.h: vx_hybrid_device_pieces and vx_hybrid_verify_files / _range
 // (kernels in sha1_kernels.hip, sha1_tail_kernels.hip and sha256_kernels.hip;
-// the rounds in vx_hybrid_rounds.hpp), and the launch of a hybrid download
-// slot (launch_hybrid_slot; the vx_hybrid_submit entries themselves sit with
-// the other submits in vx_engine.hip, the host-only part in vx_hybrid_slot.hpp).
+// the rounds in vx_hybrid_rounds.hpp), and the two tuning kernel entries.  The
+// hybrid download path (vx_hybrid_submit) is in vx_slots.hip.
 #include "vx_chunk_pipe.hpp"
 #include "vx_hybrid_rounds.hpp"
 
 using namespace vxe;
 
 namespace {
-
-// d_work of vx_hybrid_device_pieces (vx_hash.h): the merkle piece kernel's
-// work, then per piece 24 bytes of uint64 tables, 28 of uint32 and 2 verdicts.
-uint64_t merkle_work_bytes(uint32_t n, uint32_t log2_width) {
-    return log2_width > 8 ? align_up((((uint64_t)n << (log2_width - 8)) * 32) + n, 16) : 0;
-}
 
 // What one files call owns on the device and in pinned memory; gone when it
 // returns (a re-verify is once per torrent; the slots and stages stay with the
@@ -294,111 +287,6 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
 
 }  // namespace
 
-// A hybrid download slot's launch (vx_hybrid_submit).  Both
-// hashes read the one copy in the arena, so the slot is never zero-copy:
-//   1. one H2D of the whole metadata block, then the copies or the gather, on
-//      the slot's stream; `copied`;
-//   2. the context's side stream waits for `copied` and runs the merkle piece
-//      path with no expected rows; `hy_joined`;
-//   3. the slot's stream hashes every piece's whole data blocks: an unpadded
-//      piece's chunk is final and emits its digest, a padded one keeps its state;
-//   4. the slot's stream waits for `hy_joined` and runs the finish kernel;
-//   5. D2H of digests, roots and verdicts; `done`.
-// So the merkle work hides beside the SHA-1 chain, as it does when the two
-// submits of a piece land in two slots.
-int vxe::launch_hybrid_slot(vx_ctx* c, int si) {
-    Slot& s = c->slots[si];
-    const uint32_t n = s.n;
-    hipStream_t cs = s.stream;
-    if (!c->hy_stream) {
-        // High priority, as the re-verify's copy stream (vx_chunk_pipe.hpp): HIP keeps a
-        // priority's streams on hardware queues of their own.  At the default priority the
-        // side stream shared a queue with one slot's stream, and every other slot's merkle
-        // kernel (0.7 ms, and what its finish kernel waits for) queued behind that slot's
-        // 3 ms chain (profiles/hybrid/async.json, "side_stream").
-        int least = 0, greatest = 0;
-        VX_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        VX_HIP(hipStreamCreateWithPriority(&c->hy_stream, hipStreamNonBlocking, greatest));
-    }
-    const uint32_t K = s.v2_kmax;
-    const uint64_t need = K > 8 ? ((uint64_t)n << (K - 8)) * 32 + n : 0;
-    if (need > s.tops_cap) {
-        if (s.d_tops) (void)hipFree(s.d_tops);
-        s.d_tops = nullptr;
-        s.tops_cap = 0;
-        if (hipMalloc(&s.d_tops, need) != hipSuccess) return fail(VX_ENOMEM, "hybrid tile tops allocation failed");
-        s.tops_cap = need;
-    }
-    // pack what the submits filled in (vx_hybrid_slot::Pack)
-    const vx_hybrid_slot::Pack p = vx_hybrid_slot::pack(n);
-    uint8_t* h = s.h_hy;
-    auto h64 = [&](size_t o) { return reinterpret_cast<uint64_t*>(h + o); };
-    auto h32 = [&](size_t o) { return reinterpret_cast<uint32_t*>(h + o); };
-    std::memcpy(h + p.offsets, s.h_offsets, (size_t)n * 8);
-    std::memset(h + p.poffs, 0, (size_t)n * 8);
-    std::memcpy(h + p.src, s.h_src, (size_t)n * 8);
-    std::memcpy(h + p.lens, s.h_lens, (size_t)n * 4);
-    std::memcpy(h + p.rows, s.h_pidx, (size_t)n * 4);
-    std::memcpy(h + p.tfirst, s.h_tfirst, (size_t)(n + 1) * 4);
-    for (uint32_t i = 0; i < n; ++i) {
-        const vx_hybrid_slot::Lane& l = s.hy_lanes[i];
-        const Slot::HybridRows& r = s.hy_rows[i];
-        h64(p.tail_offs)[i] = l.tail_off;
-        h64(p.totals)[i] = l.total;
-        h32(p.pads)[i] = l.pad;
-        h32(p.chunks)[i] = l.chunk;
-        h32(p.ident)[i] = i;
-        std::memcpy(h + p.exp_sha1 + (size_t)i * 20, r.sha1, 20);
-        std::memcpy(h + p.exp_roots + (size_t)i * 32, r.root, 32);
-        h[p.flags + i] = l.flags;
-        h[p.log2w + i] = r.log2w;
-    }
-    uint8_t* d = s.d_hy;
-    auto d64 = [&](size_t o) { return reinterpret_cast<uint64_t*>(d + o); };
-    auto d32 = [&](size_t o) { return reinterpret_cast<uint32_t*>(d + o); };
-    if (int rc = chain_h2d(c, si)) return rc;
-    VX_HIP(hipMemcpyAsync(d, h, p.copy_bytes, hipMemcpyHostToDevice, cs));
-    for (const DirectRun& r : s.druns)
-        VX_HIP(hipMemcpyAsync(s.d_arena + r.lo, r.host, r.hi - r.lo, hipMemcpyHostToDevice, cs));
-    for (const Run& r : s.runs)
-        VX_HIP(hipMemcpyAsync(s.d_arena + r.lo, s.h_stage + r.lo, r.hi - r.lo, hipMemcpyHostToDevice, cs));
-    if (s.gtiles) {
-        const uint32_t grid = s.bytes >= (uint64_t)n << 21 ? 128u : 0u;  // as launch_slot_impl
-        hipError_t e = vx::launch_gather(d64(p.src), d64(p.offsets), d32(p.lens), d32(p.tfirst), n, s.gtiles,
-                                         s.d_arena, cs, grid);
-        if (e != hipSuccess) return hip_fail(e, "gather launch");
-        c->stats.gather_tiles += s.gtiles;
-    }
-    VX_HIP(hipEventRecord(s.copied, cs));
-    mark_launched(c, si);
-    // the merkle side, beside the chain
-    VX_HIP(hipStreamWaitEvent(c->hy_stream, s.copied, 0));
-    hipError_t e = vx::launch_merkle_pieces(s.d_arena, d64(p.offsets), d32(p.lens), d + p.log2w, n, K, s.d_tops,
-                                            s.d_roots, nullptr, nullptr, c->hy_stream);
-    if (e != hipSuccess) return hip_fail(e, "hybrid merkle piece kernel launch");
-    VX_HIP(hipEventRecord(s.hy_joined, c->hy_stream));
-    // the SHA-1 side: whole data blocks, then the join and the finish kernel
-    uint32_t* d_states = d32(p.states);
-    e = vx::launch_chunk(s.d_arena, d64(p.offsets), d32(p.chunks), n, d32(p.ident), d64(p.poffs), d64(p.totals),
-                         d_states, s.d_digests, nullptr, nullptr, cs);
-    if (e != hipSuccess) return hip_fail(e, "hybrid chunk kernel launch");
-    VX_HIP(hipStreamWaitEvent(cs, s.hy_joined, 0));
-    const uint8_t* exp1 = s.use_table ? c->d_hy_sha1 : d + p.exp_sha1;
-    const uint8_t* exp2 = s.use_table ? c->d_hy_roots : d + p.exp_roots;
-    e = vx::launch_hybrid_finish(s.d_arena, d64(p.tail_offs), d32(p.lens), d32(p.pads), n, s.hy_total ? s.hy_total : 64,
-                                 d_states, s.d_digests, s.d_roots, exp1, exp2, s.use_table ? d32(p.rows) : nullptr,
-                                 d + p.flags, s.d_matched, cs);
-    if (e != hipSuccess) return hip_fail(e, "hybrid finish kernel launch");
-    VX_HIP(hipMemcpyAsync(s.h_digests, s.d_digests, (size_t)n * 20, hipMemcpyDeviceToHost, cs));
-    VX_HIP(hipMemcpyAsync(s.h_roots, s.d_roots, (size_t)n * 32, hipMemcpyDeviceToHost, cs));
-    VX_HIP(hipMemcpyAsync(s.h_matched, s.d_matched, n, hipMemcpyDeviceToHost, cs));
-    VX_HIP(hipEventRecord(s.done, cs));
-    s.state = Slot::INFLIGHT;
-    s.seq = c->seq++;
-    c->stats.batches++;
-    return 0;
-}
-
 extern "C" {
 
 int vx_hybrid_device_pieces(const void* d_base, const uint64_t* d_offsets, const uint32_t* d_lens,
@@ -423,7 +311,9 @@ int vx_hybrid_device_pieces(const void* d_base, const uint64_t* d_offsets, const
     if (n == 0) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     uint8_t* w = static_cast<uint8_t*>(d_work);
-    uint8_t* tab = w + merkle_work_bytes(n, log2_width);
+    // d_work (vx_hash.h): the merkle piece kernel's work, then per piece 24
+    // bytes of uint64 tables, 28 of uint32 and 2 verdicts
+    uint8_t* tab = w + align_up(vx::merkle_pieces_work(n, log2_width), 16);
     uint64_t* tail_offs = reinterpret_cast<uint64_t*>(tab);
     uint64_t* poffs = tail_offs + n;
     uint64_t* tlens = poffs + n;

@@ -1,7 +1,8 @@
 // vx_hybrid_slot.hpp — the host-only part of the hybrid download path
 // (vx_hybrid_submit): the argument check of one piece, the
 // values its lane takes in the chunked SHA-1 kernel and the finish kernel, and
-// where a launch's metadata lies in the slot's one packed block.  No HIP
+// where a launch's metadata lies in the slot's one packed block (vx_slots.hip
+// submits and launches with them).  No HIP
 // dependency: tests/native/hybrid_slot_dump.cpp runs it as a stand-alone
 // program under ASan + UBSan against a Python model.
 #pragma once
@@ -21,8 +22,8 @@ inline uint64_t widest_piece(uint32_t max_piece_len) {
     return w;
 }
 
-// The check of vx_hybrid_submit's numbers (vx_hash.h), in the order of
-// vx_merkle_submit's: 0, or VX_ERANGE / VX_EINVAL with *why set.
+// The check of vx_hybrid_submit's numbers (vx_hash.h), and with pad_len = 0
+// of vx_merkle_submit's: 0, or VX_ERANGE / VX_EINVAL with *why set.
 inline int check(uint32_t len, uint32_t pad_len, uint32_t log2w, uint32_t max_piece_len, const char** why) {
     const char* dummy;
     if (!why) why = &dummy;

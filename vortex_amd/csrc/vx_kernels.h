@@ -1,5 +1,7 @@
-// vx_kernels.h — internal launch interface between the C-ABI layer
-// (vx_engine.hip) and the kernels (sha1_kernels.hip, vx_synth.hip).
+// vx_kernels.h — internal launch interface between the C-ABI layer (the host
+// units: vx_engine.hip, vx_slots.hip, vx_reverify.hip, vx_split.hip,
+// vx_merkle.hip, vx_hybrid.hip) and the kernels (sha1_kernels.hip,
+// sha1_tail_kernels.hip, sha256_kernels.hip, vx_gather.hip, vx_synth.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -140,6 +142,9 @@ hipError_t launch_merkle_ragged(const uint8_t* base, const uint64_t* offsets, co
 // unused.  Wider: work = tile tops ((n << (log2_width-8)) * 32 bytes) | log2w
 // of the tops' trees (n bytes), both written by the piece kernel, then the
 // node kernel over the tops.
+inline uint64_t merkle_pieces_work(uint32_t n, uint32_t log2_width) {  // bytes of `work`
+    return log2_width > 8 ? ((uint64_t)n << (log2_width - 8)) * 32 + n : 0;
+}
 hipError_t launch_merkle_pieces(const uint8_t* base, const uint64_t* offsets, const uint32_t* lens,
                                 const uint8_t* log2w, uint32_t n, uint32_t log2_width, uint8_t* work, uint8_t* roots,
                                 const uint8_t* expected, uint8_t* matched, hipStream_t stream);
