@@ -863,6 +863,140 @@ int vx_merkle_verify_proofs(vx_ctx* ctx, const uint8_t* hashes, uint64_t n_rows,
                             uint32_t n, const uint8_t* expected, uint32_t n_expected, uint8_t* matched_out,
                             uint8_t* tops_out);
 
+/* ---- Hashing: from files to `pieces`, `piece layers` and `pieces root` ---
+ * Every entry above checks hashes that somebody else made.  The entries below
+ * make them: what a client needs to create a torrent from a directory, and what
+ * a seeder needs to answer BEP 52 hash requests.  Bencoding is the caller's.
+ *
+ * Layer trees.  Take a layer of m >= 1 rows of 32 bytes standing `height`
+ * levels above the leaves, K = ceil(log2 m).  Its tree has levels k = 0..K;
+ * level k holds n_k = ceil(m / 2^k) rows; level 0 is the layer; row j of level
+ * k >= 1 is SHA-256(L || R) with L = row 2j of level k - 1 and R = row 2j + 1 of
+ * level k - 1, or pad(height + k - 1) when that level has no such row.  Rows
+ * that cover no row of the layer are pad hashes and are not stored.  The tree
+ * is its levels back to back, level 0 first: vx_merkle_tree_rows(m) = sum of
+ * n_k rows (at most 2m + K), the last of them the layer's root (what
+ * vx_merkle_device_root and vx_merkle_device_layers give).  m = 1 is one row. */
+uint64_t vx_merkle_tree_rows(uint64_t m);
+
+/* One workgroup in one pass of vx_merkle_device_trees; 16 bytes, read as words.
+ * The tile covers rows [512 * tile, 512 * tile + rows) of a level of level_rows
+ * rows of one layer's tree, rows = min(512, level_rows - 512 * tile), and
+ * reduces them by 9 levels when level_rows > 512 and by ceil(log2 level_rows)
+ * otherwise. */
+typedef struct vx_merkle_tree_tile {
+    uint32_t src_row;    /* the level's first row where it is read: pass 0 a row of d_hashes, later = dst_row */
+    uint32_t dst_row;    /* the level's first row in d_tree                                                  */
+    uint32_t level_rows; /* rows of the level (pass p: level 9p of the layer's tree)                         */
+    uint32_t tile;       /* which 512 rows of the level                                                      */
+} vx_merkle_tree_tile;
+struct vx_merkle_tree_plan {
+    uint32_t n_layers, passes;       /* passes 0..4 */
+    uint64_t rows;                   /* sum of counts: the rows of d_hashes */
+    uint64_t tree_rows;              /* 32-byte rows d_tree must hold */
+    uint32_t n_tiles, pass_tiles[4]; /* tiles of pass p lie consecutively, pass after pass */
+    uint32_t _pad;
+};
+/* Plan the trees of n_layers layers of counts[f] >= 1 rows; host only.  The
+ * pass rule is vx_merkle_layers_plan's.  tiles == NULL fills *plan only;
+ * otherwise tiles[0..n_tiles) are written.  tree_off (may be NULL) gets
+ * n_layers + 1 numbers: layer f's tree is rows [tree_off[f], tree_off[f + 1])
+ * of d_tree, its root row tree_off[f + 1] - 1.  VX_EINVAL as
+ * vx_merkle_layers_plan, and when the trees together hold 2^32 rows or more. */
+int vx_merkle_tree_plan(const uint32_t* counts, uint32_t n_layers, struct vx_merkle_tree_plan* plan,
+                        vx_merkle_tree_tile* tiles, size_t tiles_cap, uint64_t* tree_off);
+/* Execute a plan: plan->passes launches (n_layers == 0 launches nothing).
+ * d_hashes: plan->rows rows, the layers back to back, not modified; d_tiles: a
+ * device copy of the planner's tiles; d_tree: plan->tree_rows rows.  Pass 0
+ * reads the layers and, in the same launch, copies each into level 0 of its
+ * tree; pass p > 0 reads level 9p of every tree that reaches it from d_tree
+ * itself, where pass p - 1 wrote it.  No workgroup reads a row that another
+ * workgroup of the same launch writes.  There is no roots array: the root of
+ * layer f is row tree_off[f + 1] - 1.  height <= 64; d_hashes and d_tree
+ * 16-byte, d_tiles 4-byte aligned; d_tree must not overlap d_hashes.  The tiles
+ * are device-resident and not checked here.  Enqueue-only. */
+int vx_merkle_device_trees(const void* d_hashes, const struct vx_merkle_tree_plan* plan,
+                           const vx_merkle_tree_tile* d_tiles, uint32_t height, void* d_tree, void* stream);
+/* The same on a context, for layers in host memory (a client that has `piece
+ * layers` from a .torrent and starts seeding): synchronous, on a stream and
+ * device buffers of its own, as vx_merkle_verify_layers; it touches neither
+ * the slots nor vx_get_stats and does not return VX_EBUSY while async pieces
+ * are pending.  hashes = the layers back to back; tree_out = the trees back to
+ * back (vx_merkle_tree_plan's tree_off; sum of vx_merkle_tree_rows(counts[f])
+ * rows); roots_out (may be NULL) gets n_layers * 32 bytes. */
+int vx_merkle_build_trees(vx_ctx* ctx, const uint8_t* hashes, const uint32_t* counts, uint32_t n_layers,
+                          uint32_t height, uint8_t* tree_out, uint8_t* roots_out);
+/* One `hashes` message out of a tree; host only, a pure lookup that hashes
+ * nothing.  tree: the tree of an m-row layer at `height`.  Writes (span +
+ * uncles) * 32 bytes to out in the row order of vx_merkle_proof: rows
+ * [pos * span, (pos + 1) * span) of level `level`, then uncle t = row
+ * (pos >> t) ^ 1 of level level + log2(span) + t.  A row at or past its level's
+ * n_k, or of a level above K, is the pad hash of its height.  VX_EINVAL: span
+ * not a power of two in 1..512, uncles > 64, level > K, height > 64, m == 0, or
+ * pos * span >= n_level (a span without a row of the level).  Proofs at the
+ * 16 KiB leaf level need the leaf layer, which the calls below do not keep. */
+int vx_merkle_tree_proof(const uint8_t* tree, uint32_t m, uint32_t height, uint32_t level, uint64_t pos,
+                         uint32_t span, uint32_t uncles, uint8_t* out);
+
+/* The trees of a v2 or hybrid torrent's files, host only: counts_out[f] (nfiles
+ * numbers, may be NULL) is the rows of file f's layer: 0 for an empty file, 1
+ * for a file of at most piece_length bytes (the row is its `pieces root`),
+ * else its piece count (the rows are its `piece layers` entry, standing
+ * log2(piece_length / VX_MERKLE_BLOCK) levels above the leaves).
+ * tree_off_out (nfiles + 1 numbers, may be NULL): file f's tree is rows
+ * [tree_off_out[f], tree_off_out[f + 1]) of tree_out below, empty for an empty
+ * file; a non-empty file's `pieces root` is row tree_off_out[f + 1] - 1.
+ * Returns the total rows, or VX_EINVAL (piece_length not a power of two from
+ * VX_MERKLE_BLOCK to 2 GiB, a NULL file_lengths). */
+int64_t vx_merkle_tree_layout(const uint64_t* file_lengths, size_t nfiles, uint32_t piece_length,
+                              uint32_t* counts_out, uint64_t* tree_off_out);
+
+/* Hash a v1 torrent's files into its `pieces` table: vx_verify_files without
+ * an expected table (layout, readers and limits are that call's; the pieces
+ * always stream as resumable chunk rounds).  digests_out[20*i..] is the SHA-1
+ * of piece i; ok_out[i] (may be NULL) is 1 iff every byte of piece i was read.
+ * A piece with ok == 0 has an all-zero digest.  Returns the number of pieces
+ * that hit an I/O error, or a VX_E* code.  Common to the hash calls: VX_EBUSY
+ * while async pieces are pending; they count into vx_get_stats
+ * (pieces_completed, bytes_completed, batches or chunk_rounds as the verify
+ * call of the same kind; pieces_mismatched is untouched) and fill
+ * vx_last_verify as that verify call does. */
+int64_t vx_hash_files(vx_ctx* ctx, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                      uint32_t piece_length, size_t n_pieces, uint8_t* digests_out, uint8_t* ok_out,
+                      uint32_t io_threads);
+/* Pieces [first, first + count) only: digests_out has count * 20 bytes, ok_out
+ * count bytes. */
+int64_t vx_hash_files_range(vx_ctx* ctx, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                            uint32_t piece_length, size_t n_pieces, size_t first, size_t count,
+                            uint8_t* digests_out, uint8_t* ok_out, uint32_t io_threads);
+/* Hash a v2 torrent's files: layout, numbering and limits are
+ * vx_merkle_verify_files' (piece_length is not bounded by max_piece_len).
+ * rows_out (n_pieces * 32 bytes) gets the rows that call takes as `expected`.
+ * tree_out (may be NULL, then tree_rows is ignored) gets the layer trees of
+ * every non-empty file in file order, as vx_merkle_tree_layout lays them out,
+ * and tree_rows must equal that call's result (VX_EINVAL otherwise).  The trees
+ * are built on the device from the call's own row table after the last round
+ * and come back in one copy.  A piece with ok == 0 has an all-zero row, and a
+ * file with any such piece has an all-zero tree: no tree is published over
+ * bytes that were not read. */
+int64_t vx_merkle_hash_files(vx_ctx* ctx, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                             uint32_t piece_length, size_t n_pieces, uint8_t* rows_out, uint8_t* ok_out,
+                             uint8_t* tree_out, uint64_t tree_rows, uint32_t io_threads);
+/* Pieces [first, first + count) only; no tree. */
+int64_t vx_merkle_hash_files_range(vx_ctx* ctx, const char* const* paths, const uint64_t* file_lengths,
+                                   size_t nfiles, uint32_t piece_length, size_t n_pieces, size_t first, size_t count,
+                                   uint8_t* rows_out, uint8_t* ok_out, uint32_t io_threads);
+/* Hash a hybrid torrent's files in one pass: vx_hybrid_verify_files with both
+ * expected tables absent.  sha1_out[20*i..] is taken over piece i's data plus
+ * its implied pad zeros, as that call defines it; rows_out, ok_out, tree_out
+ * and tree_rows as for vx_merkle_hash_files. */
+int64_t vx_hybrid_hash_files(vx_ctx* ctx, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                             uint32_t piece_length, size_t n_pieces, uint8_t* sha1_out, uint8_t* rows_out,
+                             uint8_t* ok_out, uint8_t* tree_out, uint64_t tree_rows, uint32_t io_threads);
+int64_t vx_hybrid_hash_files_range(vx_ctx* ctx, const char* const* paths, const uint64_t* file_lengths,
+                                   size_t nfiles, uint32_t piece_length, size_t n_pieces, size_t first, size_t count,
+                                   uint8_t* sha1_out, uint8_t* rows_out, uint8_t* ok_out, uint32_t io_threads);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,6 +58,10 @@ EXPORTS = (
     "vx_merkle_verify_proofs",
     "vx_hybrid_device_pieces", "vx_hybrid_verify_files", "vx_hybrid_verify_files_range",
     "vx_hybrid_submit", "vx_hybrid_set_piece_tables", "vx_hybrid_submit_piece", "vx_hybrid_poll",
+    "vx_merkle_tree_rows", "vx_merkle_tree_plan", "vx_merkle_device_trees", "vx_merkle_build_trees",
+    "vx_merkle_tree_proof", "vx_merkle_tree_layout",
+    "vx_hash_files", "vx_hash_files_range", "vx_merkle_hash_files", "vx_merkle_hash_files_range",
+    "vx_hybrid_hash_files", "vx_hybrid_hash_files_range",
 )
 # ... plus include/vx_tuning.h and include/vx_synth.h: libvortex_amd_tuning.so only.
 TUNING_EXPORTS = (
@@ -109,6 +113,20 @@ class vx_merkle_layers_plan(ctypes.Structure):
     struct goes by its tag, `struct vx_merkle_layers_plan`."""
     _fields_ = [("n_layers", ctypes.c_uint32), ("passes", ctypes.c_uint32), ("rows", ctypes.c_uint64),
                 ("work_rows", ctypes.c_uint64), ("n_tiles", ctypes.c_uint32), ("pass_tiles", ctypes.c_uint32 * 4),
+                ("_pad", ctypes.c_uint32)]
+
+
+class vx_merkle_tree_tile(ctypes.Structure):
+    """One workgroup in one pass of vx_merkle_device_trees: 16 bytes."""
+    _fields_ = [("src_row", ctypes.c_uint32), ("dst_row", ctypes.c_uint32), ("level_rows", ctypes.c_uint32),
+                ("tile", ctypes.c_uint32)]
+
+
+class vx_merkle_tree_plan(ctypes.Structure):
+    """What vx_merkle_tree_plan (the function) fills: 48 bytes.  In C the
+    struct goes by its tag, `struct vx_merkle_tree_plan`."""
+    _fields_ = [("n_layers", ctypes.c_uint32), ("passes", ctypes.c_uint32), ("rows", ctypes.c_uint64),
+                ("tree_rows", ctypes.c_uint64), ("n_tiles", ctypes.c_uint32), ("pass_tiles", ctypes.c_uint32 * 4),
                 ("_pad", ctypes.c_uint32)]
 
 
@@ -271,6 +289,24 @@ def _declare(L: ctypes.CDLL, tuning: bool = False) -> None:
         "vx_hybrid_set_piece_tables": ([vp, vp, vp, c.c_uint32], c.c_int),
         "vx_hybrid_submit_piece": ([vp, c.c_uint64, vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32], c.c_int),
         "vx_hybrid_poll": ([vp, c.POINTER(vx_hybrid_completion), c.c_size_t], c.c_int64),
+        "vx_merkle_tree_rows": ([c.c_uint64], c.c_uint64),
+        "vx_merkle_tree_plan": ([vp, c.c_uint32, c.POINTER(vx_merkle_tree_plan), vp, c.c_size_t, vp], c.c_int),
+        "vx_merkle_device_trees": ([vp, c.POINTER(vx_merkle_tree_plan), vp, c.c_uint32, vp, vp], c.c_int),
+        "vx_merkle_build_trees": ([vp, vp, vp, c.c_uint32, c.c_uint32, vp, vp], c.c_int),
+        "vx_merkle_tree_proof": ([vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint64, c.c_uint32, c.c_uint32, vp],
+                                 c.c_int),
+        "vx_merkle_tree_layout": ([vp, c.c_size_t, c.c_uint32, vp, vp], c.c_int64),
+        "vx_hash_files": ([vp, vp, vp, c.c_size_t, c.c_uint32, c.c_size_t, vp, vp, c.c_uint32], c.c_int64),
+        "vx_hash_files_range": ([vp, vp, vp, c.c_size_t, c.c_uint32, c.c_size_t, c.c_size_t, c.c_size_t, vp, vp,
+                                 c.c_uint32], c.c_int64),
+        "vx_merkle_hash_files": ([vp, vp, vp, c.c_size_t, c.c_uint32, c.c_size_t, vp, vp, vp, c.c_uint64,
+                                  c.c_uint32], c.c_int64),
+        "vx_merkle_hash_files_range": ([vp, vp, vp, c.c_size_t, c.c_uint32, c.c_size_t, c.c_size_t, c.c_size_t, vp,
+                                        vp, c.c_uint32], c.c_int64),
+        "vx_hybrid_hash_files": ([vp, vp, vp, c.c_size_t, c.c_uint32, c.c_size_t, vp, vp, vp, vp, c.c_uint64,
+                                  c.c_uint32], c.c_int64),
+        "vx_hybrid_hash_files_range": ([vp, vp, vp, c.c_size_t, c.c_uint32, c.c_size_t, c.c_size_t, c.c_size_t, vp,
+                                        vp, vp, c.c_uint32], c.c_int64),
     }
     if tuning:
         sig.update({

@@ -464,11 +464,11 @@ __device__ __forceinline__ uint4 pick(bool c, const uint4 a, const uint4 b) {
     return make_uint4(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w);
 }
 
-// The tile reduction of the layers and proofs kernels: rows [row0, row0 + rows)
-// of src, filled to 1 << levels with the pad row, reduced to t row 0.  rows <=
-// kTile, levels <= kTileLog2; every thread of the workgroup calls this.
-__device__ __forceinline__ void reduce_rows(Rows& t, const uint4* src, uint64_t row0, uint32_t rows, uint32_t levels,
-                                            const uint4 pad_lo, const uint4 pad_hi) {
+// Rows [row0, row0 + rows) of src into the tile, the rest of it filled with the
+// pad row.  rows <= kTile; every thread of the workgroup calls this (a barrier
+// at the end).
+__device__ __forceinline__ void load_rows(Rows& t, const uint4* src, uint64_t row0, uint32_t rows, const uint4 pad_lo,
+                                          const uint4 pad_hi) {
     const uint32_t i = threadIdx.x;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -482,6 +482,14 @@ __device__ __forceinline__ void reduce_rows(Rows& t, const uint4* src, uint64_t 
         t.hi[r] = hi;
     }
     __syncthreads();
+}
+
+// The tile reduction of the layers and proofs kernels: rows [row0, row0 + rows)
+// of src, filled to 1 << levels with the pad row, reduced to t row 0.  rows <=
+// kTile, levels <= kTileLog2; every thread of the workgroup calls this.
+__device__ __forceinline__ void reduce_rows(Rows& t, const uint4* src, uint64_t row0, uint32_t rows, uint32_t levels,
+                                            const uint4 pad_lo, const uint4 pad_hi) {
+    load_rows(t, src, row0, rows, pad_lo, pad_hi);
     for (uint32_t L = 0; L < levels; ++L) reduce_level(t, (1u << levels) >> (L + 1));
 }
 
@@ -516,6 +524,55 @@ __global__ __launch_bounds__(kNodeBlock) void merkle_layers_kernel(const uint8_t
     }
 }
 
+// Rows [0, count) of the LDS tile to tree rows [row0, row0 + count): lane l of a
+// step stores uint4 l of the run (row l / 2, its low or high half), so a wave
+// writes 1 KiB of consecutive bytes.  The caller has a barrier behind the
+// tile's last write; the tile is only read here.
+__device__ __forceinline__ void store_rows(const Rows& t, uint8_t* tree, uint64_t row0, uint32_t count) {
+    uint4* dst = reinterpret_cast<uint4*>(tree) + row0 * 2;
+    for (uint32_t u = threadIdx.x; u < 2 * count; u += kNodeBlock) dst[u] = (u & 1) ? t.hi[u >> 1] : t.lo[u >> 1];
+}
+
+// One pass of the layer trees (vx_merkle_device_trees): workgroup b executes
+// tile tiles[b] of the host's plan (vx_merkle_tree.hpp).  The tile is rows
+// [512 * tile, +rows) of a level of level_rows rows; it is loaded as
+// reduce_rows loads it, the rest filled with the pass's pad hash, and after
+// each level of the reduction the rows of that level that exist,
+// ceil(rows / 2^j), go to their place in the tree: the next level starts
+// level_rows rows further on and is half as long, and the tile's rows start at
+// half the position.  in: d_hashes in pass 0 (copy0 set: the loaded rows are
+// also stored, as level 0 of the tree), the tree itself later; a later pass
+// reads level 9p only, which the launch before it wrote, and writes the levels
+// above it.  rows and levels are not taken from the descriptor but follow from
+// level_rows and tile, so whatever the descriptor holds the tile stays inside
+// LDS (the clamp of merkle_layers_kernel).
+__global__ __launch_bounds__(kNodeBlock) void merkle_tree_kernel(const uint8_t* in,
+                                                                 const vx_merkle_tree_tile* __restrict__ tiles,
+                                                                 uint4 pad_lo, uint4 pad_hi, uint32_t copy0,
+                                                                 uint8_t* tree) {
+    __shared__ Rows t;
+    const uint32_t* d = reinterpret_cast<const uint32_t*>(tiles + blockIdx.x);  // (workgroup-uniform: scalar loads)
+    const uint32_t src_row = d[0], dst_row = d[1], level_rows = d[2], tile = d[3];
+    uint64_t pos = (uint64_t)tile << kTileLog2;
+    const uint64_t left = pos < level_rows ? level_rows - pos : 0;
+    const uint32_t rows = left < kTile ? (uint32_t)left : kTile;
+    uint32_t levels = kTileLog2;
+    if (level_rows <= kTile) levels = level_rows > 1 ? 32u - (uint32_t)__builtin_clz(level_rows - 1) : 0;
+    load_rows(t, reinterpret_cast<const uint4*>(in), (uint64_t)src_row + pos, rows, pad_lo, pad_hi);
+    uint64_t base = dst_row, n = level_rows;
+    if (copy0) store_rows(t, tree, base + pos, rows);
+    for (uint32_t j = 1; j <= levels; ++j) {
+        reduce_level(t, (1u << levels) >> j);
+        base += n;
+        n = (n + 1) >> 1;
+        pos >>= 1;
+        store_rows(t, tree, base + pos, (rows + (1u << j) - 1) >> j);
+    }
+}
+
+static_assert(sizeof(vx_merkle_tree_tile) == 16 && offsetof(vx_merkle_tree_tile, dst_row) == 4 &&
+                  offsetof(vx_merkle_tree_tile, level_rows) == 8 && offsetof(vx_merkle_tree_tile, tile) == 12,
+              "merkle_tree_kernel reads the descriptor as words");
 static_assert(sizeof(vx_merkle_tile) == 16 && offsetof(vx_merkle_tile, rows) == 8 &&
                   offsetof(vx_merkle_tile, levels) == 10 && offsetof(vx_merkle_tile, last) == 11,
               "merkle_layers_kernel reads the descriptor as words");
@@ -714,6 +771,22 @@ hipError_t launch_merkle_layers(const uint8_t* hashes, const struct vx_merkle_la
         memcpy(pad, pads[p], 32);
         hipLaunchKernelGGL(merkle_layers_kernel, dim3(plan.pass_tiles[p]), dim3(kNodeBlock), 0, stream,
                            p == 0 ? hashes : work, tiles + first, pad[0], pad[1], work, roots, expected, matched);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        first += plan.pass_tiles[p];
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_merkle_trees(const uint8_t* hashes, const struct vx_merkle_tree_plan& plan,
+                               const vx_merkle_tree_tile* tiles, uint8_t* tree, const uint8_t (*pads)[32],
+                               hipStream_t stream) {
+    uint32_t first = 0;
+    for (uint32_t p = 0; p < plan.passes; ++p) {
+        uint4 pad[2];  // rows are bytes: the words as the device loads them
+        memcpy(pad, pads[p], 32);
+        hipLaunchKernelGGL(merkle_tree_kernel, dim3(plan.pass_tiles[p]), dim3(kNodeBlock), 0, stream,
+                           p == 0 ? hashes : tree, tiles + first, pad[0], pad[1], p == 0 ? 1u : 0u, tree);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         first += plan.pass_tiles[p];

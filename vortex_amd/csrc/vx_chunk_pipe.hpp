@@ -14,6 +14,7 @@ struct FileVerify {
     uint8_t* matched_out;
     std::vector<uint8_t>& bad;
     uint64_t done = 0;
+    uint8_t* digests_out = nullptr;  // vx_hash_files: no expected table, the digests come back instead
 
     void consume() {
         while (!c->done.empty()) {
@@ -33,7 +34,8 @@ struct FileVerify {
 // (vx_reverify.hip); verify_split is the split's driver (vx_split.hip).
 int64_t verify_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
                           uint32_t piece_length, const uint8_t* expected, size_t n_pieces, size_t first,
-                          size_t count, uint8_t* matched_out, uint32_t io_threads, vx_split* sp);
+                          size_t count, uint8_t* matched_out, uint32_t io_threads, vx_split* sp,
+                          uint8_t* digests_out = nullptr);
 int verify_split(FileVerify& fv, vx_files::Readers& rd, vx_split* sp, uint64_t n, uint32_t pl, uint64_t total,
                  uint64_t C, uint64_t* lowest, int regime);
 

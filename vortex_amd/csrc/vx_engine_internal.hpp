@@ -416,6 +416,13 @@ inline int64_t end_files_call(vx_ctx* c, const std::vector<int>& fds, const std:
     return nbad;
 }
 void free_merkle_files(vx_ctx* c);  // vx_merkle.hip: vx_merkle_verify_files' buffers, not its event
+// vx_merkle.hip, the end of a v2 or hybrid hash call: the layer trees of every
+// non-empty file (vx_merkle_tree_layout) from d_rows, the whole torrent's piece
+// rows on the device in piece order, into tree_out; synchronous, on st, with a
+// device block of its own.  bad[i] != 0 (piece i lacks bytes) zeroes the tree
+// of piece i's file.
+int file_trees(vx_ctx* c, const uint8_t* d_rows, const uint64_t* file_lengths, size_t nfiles, uint32_t piece_length,
+               const std::vector<uint8_t>& bad, uint8_t* tree_out, hipStream_t st, const std::string& who);
 // vx_reverify.hip, the _multi calls.  check_contexts: no NULL, no duplicate.
 // fan_out: fn(k) for k in [0, nctx), one host thread per context (context 0,
 // and any whose thread could not start, on the caller's); the sum of the

@@ -5,6 +5,7 @@
 // hybrid download path (vx_hybrid_submit) is in vx_slots.hip.
 #include "vx_chunk_pipe.hpp"
 #include "vx_hybrid_rounds.hpp"
+#include "vx_merkle_tree.hpp"
 
 using namespace vxe;
 
@@ -66,12 +67,20 @@ struct HybridBufs {
     }
 };
 
+// sha1_out and rows_out set: the hash call (vx_hybrid_hash_files).  Both
+// expected tables are absent; the kernels write digests and rows where the
+// verify call keeps the expected ones, matched_out is the call's ok_out (may be
+// NULL), and with tree_out the files' trees are built from the rows after the
+// last round.
 int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
                           uint32_t piece_length, const uint8_t* exp_sha1, const uint8_t* exp_roots, size_t n_pieces,
-                          size_t first, size_t count, uint8_t* matched_out, uint32_t io_threads) {
-    const std::string who = "vx_hybrid_verify_files";
+                          size_t first, size_t count, uint8_t* matched_out, uint32_t io_threads,
+                          uint8_t* sha1_out = nullptr, uint8_t* rows_out = nullptr, uint8_t* tree_out = nullptr,
+                          uint64_t tree_rows = 0) {
+    const bool hashing = sha1_out && rows_out;
+    const std::string who = hashing ? "vx_hybrid_hash_files" : "vx_hybrid_verify_files";
     if (!c) return fail(VX_EINVAL, who + ": NULL context");
-    if (!paths || !file_lengths || !exp_sha1 || !exp_roots || !matched_out)
+    if (!paths || !file_lengths || (!hashing && (!exp_sha1 || !exp_roots || !matched_out)))
         return fail(VX_EINVAL, who + ": NULL paths/file_lengths/exp_sha1/exp_roots/matched_out");
     if (piece_length < VX_MERKLE_BLOCK || (piece_length & (piece_length - 1)))
         return fail(VX_EINVAL, who + ": piece_length must be a power of two >= 16384");
@@ -79,6 +88,8 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
         return fail(VX_EINVAL, who + ": n_pieces does not match the files");
     if (first > n_pieces || count > n_pieces - first) return fail(VX_EINVAL, who + ": piece range outside the torrent");
     if (count >> 32) return fail(VX_EINVAL, who + ": more than 2^32 pieces in one call");
+    if (tree_out && (uint64_t)vx_merkle::tree_layout(file_lengths, nfiles, piece_length, nullptr, nullptr) != tree_rows)
+        return fail(VX_EINVAL, who + ": tree_rows is not what vx_merkle_tree_layout returns");
     int rc = begin_bulk_call(c, who, /*need_idle=*/true);
     if (rc) return rc;
     if (count == 0) return 0;
@@ -124,8 +135,8 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
         vx_merkle::PieceCursor pc(file_lengths, nfiles, piece_length);
         pc.seek(first);
         for (size_t i = 0; i < count; ++i, pc.next()) lw[i] = (uint8_t)pc.log2w();
-        if (hipMemcpy(d_exp1, exp_sha1 + 20 * first, count * 20, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(d_exp2, exp_roots + 32 * first, count * 32, hipMemcpyHostToDevice) != hipSuccess ||
+        if ((!hashing && (hipMemcpy(d_exp1, exp_sha1 + 20 * first, count * 20, hipMemcpyHostToDevice) != hipSuccess ||
+                          hipMemcpy(d_exp2, exp_roots + 32 * first, count * 32, hipMemcpyHostToDevice) != hipSuccess)) ||
             hipMemcpy(d_lw, lw.data(), count, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemset(d_v1, 0, 2 * count) != hipSuccess ||
             hipStreamSynchronize(nullptr) != hipSuccess)  // (the slot streams do not wait for the null stream)
@@ -135,7 +146,14 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
     for (size_t f = 0; f < nfiles; ++f) fds[f] = open(paths[f], O_RDONLY | O_CLOEXEC);
     const int nthreads = io_threads ? (int)io_threads : (int)std::max(1u, std::min(16u, usable_cpus()));
     std::vector<uint8_t> bad(count, 0);
-    std::memset(matched_out, 0, count);
+    if (matched_out) std::memset(matched_out, 0, count);
+    // hashing: the digests and rows land where the verify call keeps the expected ones
+    uint8_t* const d_dig = hashing ? d_exp1 : nullptr;
+    uint8_t* const d_rows = hashing ? d_exp2 : nullptr;
+    const uint8_t* const k_exp1 = hashing ? nullptr : d_exp1;
+    const uint8_t* const k_exp2 = hashing ? nullptr : d_exp2;
+    uint8_t* const k_v1 = hashing ? nullptr : d_v1;
+    uint8_t* const k_v2 = hashing ? nullptr : d_v2;
     const size_t nslots = c->slots.size();
     const size_t depth = nslots - 1;  // reads run ahead as far as the slots allow (as vx_merkle_verify_files)
     uint64_t n_rounds = 0, n_bytes = 0, copy_bytes = 0;
@@ -217,13 +235,13 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
 #endif
             if (err == hipSuccess)
                 err = vx::launch_chunk(s.d_arena, u64(a_loff), u32(a_llen), (uint32_t)m, u32(a_lpid), u64(a_lpoff),
-                                       u64(a_ltlen), d_states, nullptr, d_exp1, d_v1, s.stream);
+                                       u64(a_ltlen), d_states, d_dig, k_exp1, k_v1, s.stream);
             if (err == hipSuccess && t) {  // the tails: after the states, beside everything else
                 err = hipEventRecord(hb.state[si], s.stream);
                 if (err == hipSuccess) err = hipStreamWaitEvent(hb.tail_stream, hb.state[si], 0);
                 if (err == hipSuccess)
                     err = vx::launch_zero_tail(s.d_arena, u64(a_toff), u32(a_tlen), u32(a_tpad), u32(a_tpid),
-                                               (uint32_t)t, piece_length, d_states, nullptr, d_exp1, d_v1,
+                                               (uint32_t)t, piece_length, d_states, d_dig, k_exp1, k_v1,
                                                hb.tail_stream);
                 if (err == hipSuccess) err = hipEventRecord(hb.tailed[si], hb.tail_stream);
             }
@@ -231,8 +249,9 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
                 err = vx::launch_merkle_blocks(s.d_arena, u32(a_rows), u32(a_lens), (uint32_t)e, d_leaves, s.stream);
             if (err == hipSuccess && r.end_window) {
                 const uint64_t k = r.w_first - first;
-                err = vx::launch_merkle_nodes(d_leaves, d_lw + k, r.w_n, r.w_log2, nullptr, d_exp2 + k * 32,
-                                              d_v2 + k, s.stream);
+                err = vx::launch_merkle_nodes(d_leaves, d_lw + k, r.w_n, r.w_log2, hashing ? d_rows + k * 32 : nullptr,
+                                              hashing ? nullptr : k_exp2 + k * 32, hashing ? nullptr : k_v2 + k,
+                                              s.stream);
             }
             if (err == hipSuccess) err = hipEventRecord(hb.chain, s.stream);
             // the slot's arena and tables are free again once its tails have read them too
@@ -258,9 +277,15 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
                 rc = fail(VX_EDEVICE, who + ": a round failed on the device");
         if (hipStreamSynchronize(hb.tail_stream) != hipSuccess && !rc)
             rc = fail(VX_EDEVICE, who + ": a tail kernel failed on the device");
-        std::vector<uint8_t> verdict(2 * count);
-        if (!rc && hipMemcpy(verdict.data(), d_v1, 2 * count, hipMemcpyDeviceToHost) != hipSuccess)
+        std::vector<uint8_t> verdict(hashing ? 0 : 2 * count);
+        if (!rc && !hashing && hipMemcpy(verdict.data(), d_v1, 2 * count, hipMemcpyDeviceToHost) != hipSuccess)
             rc = fail(VX_EDEVICE, who + ": verdict download failed");
+        if (!rc && hashing &&
+            (hipMemcpy(sha1_out, d_dig, count * 20, hipMemcpyDeviceToHost) != hipSuccess ||
+             hipMemcpy(rows_out, d_rows, count * 32, hipMemcpyDeviceToHost) != hipSuccess))
+            rc = fail(VX_EDEVICE, who + ": digest and row download failed");
+        if (!rc && tree_out)  // (the whole torrent: first == 0, count == n_pieces)
+            rc = file_trees(c, d_rows, file_lengths, nfiles, piece_length, bad, tree_out, c->slots[0].stream, who);
         vx_verify_trace& vt = c->last_verify;
         vt.tail_ms = std::chrono::duration<double, std::milli>(clk::now() - t_last_enqueue).count();
         trace_reads(vt, rd, dio, t_call);
@@ -269,7 +294,11 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
         vt.chunk_bytes = C;
         if (!rc) {
             uint64_t mism = 0;
-            for (size_t i = 0; i < count; ++i) {
+            for (size_t i = 0; i < count && hashing; ++i) {  // never a digest or row over bytes that were not read
+                if (matched_out) matched_out[i] = !bad[i];
+                if (bad[i]) std::memset(sha1_out + i * 20, 0, 20), std::memset(rows_out + i * 32, 0, 32);
+            }
+            for (size_t i = 0; i < count && !hashing; ++i) {
                 const uint8_t v = bad[i] ? 0 : (uint8_t)((verdict[i] ? 1 : 0) | (verdict[count + i] ? 2 : 0));
                 matched_out[i] = v;
                 n_failed += v != 3;
@@ -282,7 +311,7 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
         }
     }
     const int64_t ended = end_files_call(c, fds, bad, t_call, rc);
-    return ended < 0 ? ended : n_failed;
+    return ended < 0 || hashing ? ended : n_failed;
 }
 
 }  // namespace
@@ -364,6 +393,22 @@ int vx_tuning_chunk_kernel(const void* d_base, const uint64_t* d_offsets, const 
                                     d_states, static_cast<uint8_t*>(d_digests), nullptr, nullptr,
                                     static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : hip_fail(e, "vx_tuning_chunk_kernel");
+}
+
+int64_t vx_hybrid_hash_files_range(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                                   uint32_t piece_length, size_t n_pieces, size_t first, size_t count,
+                                   uint8_t* sha1_out, uint8_t* rows_out, uint8_t* ok_out, uint32_t io_threads) {
+    if (!sha1_out || !rows_out) return fail(VX_EINVAL, "vx_hybrid_hash_files: NULL sha1_out or rows_out");
+    return hybrid_files_impl(c, paths, file_lengths, nfiles, piece_length, nullptr, nullptr, n_pieces, first, count,
+                             ok_out, io_threads, sha1_out, rows_out);
+}
+
+int64_t vx_hybrid_hash_files(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                             uint32_t piece_length, size_t n_pieces, uint8_t* sha1_out, uint8_t* rows_out,
+                             uint8_t* ok_out, uint8_t* tree_out, uint64_t tree_rows, uint32_t io_threads) {
+    if (!sha1_out || !rows_out) return fail(VX_EINVAL, "vx_hybrid_hash_files: NULL sha1_out or rows_out");
+    return hybrid_files_impl(c, paths, file_lengths, nfiles, piece_length, nullptr, nullptr, n_pieces, 0, n_pieces,
+                             ok_out, io_threads, sha1_out, rows_out, tree_out, tree_rows);
 }
 
 int64_t vx_hybrid_verify_files_range(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,

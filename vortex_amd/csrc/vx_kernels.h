@@ -166,6 +166,12 @@ hipError_t launch_merkle_root(const uint8_t* layer, uint32_t n, uint8_t* work, u
 hipError_t launch_merkle_layers(const uint8_t* hashes, const struct vx_merkle_layers_plan& plan,
                                 const vx_merkle_tile* tiles, uint8_t* work, uint8_t* roots, const uint8_t* expected,
                                 uint8_t* matched, const uint8_t (*pads)[32], hipStream_t stream);
+// The trees of many layers in plan.passes launches (vx_merkle_device_trees):
+// tiles is the device copy of the planner's tiles, pads[p] the pad hash of the
+// layers' height + 9p, tree plan.tree_rows rows.
+hipError_t launch_merkle_trees(const uint8_t* hashes, const struct vx_merkle_tree_plan& plan,
+                               const vx_merkle_tree_tile* tiles, uint8_t* tree, const uint8_t (*pads)[32],
+                               hipStream_t stream);
 // Hash proofs in two launches (vx_merkle_device_proofs): the spans' roots into
 // tops, then the uncle walks, the tops in place and the verdicts.
 hipError_t launch_merkle_proofs(const uint8_t* hashes, const vx_merkle_proof* proofs, uint32_t n, uint8_t* tops,

@@ -1,8 +1,10 @@
 // vx_merkle.hip — the BitTorrent v2 merkle entries of vx_hash.h (kernels in
 // sha256_kernels.hip): vx_merkle_device_*, _verify_batch, _verify_files,
-// _layers_plan, _verify_layers, _verify_proofs.
+// _layers_plan, _verify_layers, _verify_proofs; the layer trees (_tree_plan,
+// _device_trees, _build_trees, _tree_proof, _tree_layout) and _hash_files.
 #include "vx_engine_internal.hpp"
 #include "vx_merkle_layers.hpp"
+#include "vx_merkle_tree.hpp"
 
 using namespace vxe;
 
@@ -18,6 +20,47 @@ void vxe::free_merkle_files(vx_ctx* c) {
     hipEvent_t chain = m.chain;
     m = vx_ctx::MerkleFiles{};
     m.chain = chain;
+}
+
+int vxe::file_trees(vx_ctx* c, const uint8_t* d_rows, const uint64_t* file_lengths, size_t nfiles,
+                    uint32_t piece_length, const std::vector<uint8_t>& bad, uint8_t* tree_out, hipStream_t st,
+                    const std::string& who) {
+    if (int rc = set_device(c)) return rc;
+    std::vector<uint32_t> counts;  // of the non-empty files: their pieces are d_rows, back to back
+    for (size_t f = 0; f < nfiles; ++f)
+        if (file_lengths[f]) counts.push_back((uint32_t)((file_lengths[f] + piece_length - 1) / piece_length));
+    if (counts.empty()) return 0;
+    struct vx_merkle_tree_plan plan;
+    if (vx_merkle::plan_trees(counts.data(), (uint32_t)counts.size(), &plan, nullptr, 0, nullptr))
+        return fail(VX_EINVAL, who + ": the files' trees hold 2^32 rows or more");
+    std::vector<vx_merkle_tree_tile> tiles(plan.n_tiles);
+    std::vector<uint64_t> off(counts.size() + 1);
+    (void)vx_merkle::plan_trees(counts.data(), (uint32_t)counts.size(), &plan, tiles.data(), tiles.size(), off.data());
+    uint32_t height = 0;
+    while (((uint32_t)VX_MERKLE_BLOCK << height) < piece_length) ++height;
+    uint8_t* d = nullptr;
+    if (hipMalloc(&d, plan.tree_rows * 32 + tiles.size() * sizeof(vx_merkle_tree_tile)) != hipSuccess)
+        return fail(VX_ENOMEM, who + ": tree buffer allocation failed");
+    uint8_t* d_tiles = d + plan.tree_rows * 32;
+    int rc = 0;
+    if (hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(vx_merkle_tree_tile), hipMemcpyHostToDevice, st) !=
+        hipSuccess)
+        rc = fail(VX_EDEVICE, who + ": tile upload failed");
+    if (!rc)
+        rc = vx_merkle_device_trees(d_rows, &plan, reinterpret_cast<const vx_merkle_tree_tile*>(d_tiles), height, d, st);
+    if (!rc && hipMemcpyAsync(tree_out, d, plan.tree_rows * 32, hipMemcpyDeviceToHost, st) != hipSuccess)
+        rc = fail(VX_EDEVICE, who + ": tree download failed");
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(VX_EDEVICE, who + ": the tree passes failed");
+    (void)hipFree(d);
+    if (rc) return rc;
+    uint64_t piece = 0;
+    for (size_t k = 0; k < counts.size(); ++k) {  // never a tree over bytes that were not read
+        bool any = false;
+        for (uint32_t j = 0; j < counts[k]; ++j) any |= bad[piece + j] != 0;
+        if (any) std::memset(tree_out + off[k] * 32, 0, (off[k + 1] - off[k]) * 32);
+        piece += counts[k];
+    }
+    return 0;
 }
 
 extern "C" {
@@ -427,12 +470,19 @@ static int ensure_merkle_files(vx_ctx* c, uint64_t window_rows, uint64_t entries
     return 0;
 }
 
+// rows_out set: the hash call (vx_merkle_hash_files).  No expected table; the
+// node kernels write the pieces' rows where the verify call keeps the expected
+// ones, matched_out is the call's ok_out (may be NULL), and with tree_out the
+// files' trees are built from those rows after the last round.
 static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
                                  uint32_t piece_length, const uint8_t* expected, size_t n_pieces, size_t first,
-                                 size_t count, uint8_t* matched_out, uint32_t io_threads) {
-    const char* who = "vx_merkle_verify_files";
+                                 size_t count, uint8_t* matched_out, uint32_t io_threads, uint8_t* rows_out = nullptr,
+                                 uint8_t* tree_out = nullptr, uint64_t tree_rows = 0) {
+    const bool hashing = rows_out != nullptr;
+    const char* who = hashing ? "vx_merkle_hash_files" : "vx_merkle_verify_files";
     if (!c) return fail(VX_EINVAL, std::string(who) + ": NULL context");
-    if ((nfiles && (!paths || !file_lengths)) || (n_pieces && !expected) || (count && !matched_out))
+    if (hashing ? (nfiles && (!paths || !file_lengths))
+                : ((nfiles && (!paths || !file_lengths)) || (n_pieces && !expected) || (count && !matched_out)))
         return fail(VX_EINVAL, std::string(who) + ": NULL paths/file_lengths/expected/matched_out");
     if (piece_length < VX_MERKLE_BLOCK || (piece_length & (piece_length - 1)))
         return fail(VX_EINVAL, std::string(who) + ": piece_length must be a power of two >= 16384");
@@ -440,6 +490,8 @@ static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint
         return fail(VX_EINVAL, std::string(who) + ": n_pieces does not match the files");
     if (first > n_pieces || count > n_pieces - first)
         return fail(VX_EINVAL, std::string(who) + ": piece range outside the torrent");
+    if (tree_out && (uint64_t)vx_merkle::tree_layout(file_lengths, nfiles, piece_length, nullptr, nullptr) != tree_rows)
+        return fail(VX_EINVAL, std::string(who) + ": tree_rows is not what vx_merkle_tree_layout returns");
     int rc = begin_bulk_call(c, who, /*need_idle=*/true);
     if (rc) return rc;
     if (count == 0) return 0;
@@ -465,7 +517,7 @@ static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint
         vx_merkle::PieceCursor pc(file_lengths, nfiles, piece_length);
         pc.seek(first);
         for (size_t i = 0; i < count; ++i, pc.next()) lw[i] = (uint8_t)pc.log2w();
-        if (hipMemcpy(d_exp, expected + 32 * first, count * 32, hipMemcpyHostToDevice) != hipSuccess ||
+        if ((!hashing && hipMemcpy(d_exp, expected + 32 * first, count * 32, hipMemcpyHostToDevice) != hipSuccess) ||
             hipMemcpy(d_lw, lw.data(), count, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemset(d_match, 0, count) != hipSuccess ||
             hipStreamSynchronize(nullptr) != hipSuccess)  // (the slot streams do not wait for the null stream)
@@ -475,7 +527,7 @@ static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint
     for (size_t f = 0; f < nfiles; ++f) fds[f] = open(paths[f], O_RDONLY | O_CLOEXEC);
     const int nthreads = io_threads ? (int)io_threads : (int)std::max(1u, std::min(16u, usable_cpus()));
     std::vector<uint8_t> bad(count, 0);
-    std::memset(matched_out, 0, count);
+    if (matched_out) std::memset(matched_out, 0, count);
     const size_t nslots = c->slots.size();
     // Reads run ahead as far as the slots allow: a v2 round carries no state,
     // so a slot is free again as soon as its own round's kernels are done, and
@@ -544,8 +596,9 @@ static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint
             for (const vx_merkle::Nodes& g : r.nodes) {
                 if (e != hipSuccess) break;
                 const uint64_t k = g.first - first;
-                e = vx::launch_merkle_nodes(mf.d_window + (size_t)g.row0 * 32, d_lw + k, g.n, g.log2_width, nullptr,
-                                            d_exp + k * 32, d_match + k, s.stream);
+                e = vx::launch_merkle_nodes(mf.d_window + (size_t)g.row0 * 32, d_lw + k, g.n, g.log2_width,
+                                            hashing ? d_exp + k * 32 : nullptr, hashing ? nullptr : d_exp + k * 32,
+                                            hashing ? nullptr : d_match + k, s.stream);
             }
             if (e == hipSuccess) e = hipEventRecord(mf.chain, s.stream);
             if (e == hipSuccess) e = hipEventRecord(s.done, s.stream);
@@ -564,9 +617,13 @@ static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint
         for (size_t si = 0; si < nslots; ++si)  // ... and no copy may still read one
             if (c->slots[si].stream && hipStreamSynchronize(c->slots[si].stream) != hipSuccess && !rc)
                 rc = fail(VX_EDEVICE, std::string(who) + ": a round failed on the device");
-        std::vector<uint8_t> verdict(count);
-        if (!rc && hipMemcpy(verdict.data(), d_match, count, hipMemcpyDeviceToHost) != hipSuccess)
+        std::vector<uint8_t> verdict(hashing ? 0 : count);
+        if (!rc && !hashing && hipMemcpy(verdict.data(), d_match, count, hipMemcpyDeviceToHost) != hipSuccess)
             rc = fail(VX_EDEVICE, std::string(who) + ": verdict download failed");
+        if (!rc && hashing && hipMemcpy(rows_out, d_exp, count * 32, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(VX_EDEVICE, std::string(who) + ": row download failed");
+        if (!rc && tree_out)  // (the whole torrent: first == 0, count == n_pieces)
+            rc = file_trees(c, d_exp, file_lengths, nfiles, piece_length, bad, tree_out, c->slots[0].stream, who);
         vx_verify_trace& vt = c->last_verify;
         vt.tail_ms = std::chrono::duration<double, std::milli>(clk::now() - t_last_enqueue).count();
         trace_reads(vt, rd, dio, t_call);
@@ -576,6 +633,11 @@ static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint
         if (!rc) {
             uint64_t mism = 0;
             for (size_t i = 0; i < count; ++i) {
+                if (hashing) {  // never a row over bytes that were not read
+                    if (matched_out) matched_out[i] = !bad[i];
+                    if (bad[i]) std::memset(rows_out + i * 32, 0, 32);
+                    continue;
+                }
                 matched_out[i] = verdict[i] && !bad[i] ? 1 : 0;
                 mism += !verdict[i] && !bad[i];  // I/O errors count in io_errors only
             }
@@ -746,6 +808,122 @@ int vx_merkle_verify_proofs(vx_ctx* c, const uint8_t* hashes, uint64_t n_rows, c
     VX_HIP(hipMemcpyAsync(matched_out, b.d + o_match, n, hipMemcpyDeviceToHost, b.stream));
     VX_HIP(hipStreamSynchronize(b.stream));
     return 0;
+}
+
+// ---- layer trees ("Layer trees") ----
+
+uint64_t vx_merkle_tree_rows(uint64_t m) { return vx_merkle::tree_rows(m); }
+
+int vx_merkle_tree_plan(const uint32_t* counts, uint32_t n_layers, struct vx_merkle_tree_plan* plan,
+                        vx_merkle_tree_tile* tiles, size_t tiles_cap, uint64_t* tree_off) {
+    if (!plan || (n_layers && !counts)) return fail(VX_EINVAL, "vx_merkle_tree_plan: NULL plan or counts");
+    struct vx_merkle_tree_plan pl;
+    if (vx_merkle::plan_trees(counts, n_layers, &pl, nullptr, 0, nullptr))
+        return fail(VX_EINVAL,
+                    "vx_merkle_tree_plan: a count is 0, or the layers or their trees hold 2^32 rows or more");
+    if (tiles && tiles_cap < pl.n_tiles) return fail(VX_EINVAL, "vx_merkle_tree_plan: tiles_cap < n_tiles");
+    return vx_merkle::plan_trees(counts, n_layers, plan, tiles, tiles_cap, tree_off);
+}
+
+int vx_merkle_device_trees(const void* d_hashes, const struct vx_merkle_tree_plan* plan,
+                           const vx_merkle_tree_tile* d_tiles, uint32_t height, void* d_tree, void* stream) {
+    if (!plan) return fail(VX_EINVAL, "vx_merkle_device_trees: NULL plan");
+    if (plan->n_layers == 0) return 0;
+    if (!d_hashes || !d_tiles || !d_tree) return fail(VX_EINVAL, "vx_merkle_device_trees: NULL d_hashes, d_tiles or d_tree");
+    if ((reinterpret_cast<uintptr_t>(d_hashes) | reinterpret_cast<uintptr_t>(d_tree)) & 15)
+        return fail(VX_EINVAL, "vx_merkle_device_trees: d_hashes and d_tree must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_tiles) & 3)
+        return fail(VX_EINVAL, "vx_merkle_device_trees: d_tiles must be 4-byte aligned");
+    if (height > 64) return fail(VX_EINVAL, "vx_merkle_device_trees: height > 64");
+    uint64_t tiles = 0;
+    for (uint32_t p = 0; p < 4; ++p) tiles += p < plan->passes ? plan->pass_tiles[p] : 0;
+    if (plan->passes > 4 || tiles != plan->n_tiles || (plan->tree_rows >> 32) || plan->tree_rows < plan->rows)
+        return fail(VX_EINVAL, "vx_merkle_device_trees: not a plan of vx_merkle_tree_plan (passes, pass_tiles, rows)");
+    const uintptr_t h0 = reinterpret_cast<uintptr_t>(d_hashes), t0 = reinterpret_cast<uintptr_t>(d_tree);
+    if (h0 < t0 + plan->tree_rows * 32 && t0 < h0 + plan->rows * 32)
+        return fail(VX_EINVAL, "vx_merkle_device_trees: d_tree overlaps d_hashes");
+    uint8_t pads[4][32];  // pad(height + 9p), one per pass
+    for (int p = 0; p < 4; ++p) vx_merkle_pad_hash(height + 9 * p, pads[p]);
+    hipError_t e = vx::launch_merkle_trees(static_cast<const uint8_t*>(d_hashes), *plan, d_tiles,
+                                           static_cast<uint8_t*>(d_tree), pads, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "merkle tree kernel launch");
+    return 0;
+}
+
+int vx_merkle_build_trees(vx_ctx* c, const uint8_t* hashes, const uint32_t* counts, uint32_t n_layers,
+                          uint32_t height, uint8_t* tree_out, uint8_t* roots_out) {
+    const char* who = "vx_merkle_build_trees";
+    if (!c) return fail(VX_EINVAL, std::string(who) + ": NULL context");
+    if (n_layers && (!hashes || !counts || !tree_out))
+        return fail(VX_EINVAL, std::string(who) + ": NULL hashes/counts/tree_out");
+    if (height > 64) return fail(VX_EINVAL, std::string(who) + ": height > 64");
+    if (n_layers == 0) return 0;
+    struct vx_merkle_tree_plan plan;
+    if (vx_merkle::plan_trees(counts, n_layers, &plan, nullptr, 0, nullptr))
+        return fail(VX_EINVAL, std::string(who) + ": a count is 0, or the layers or their trees hold 2^32 rows or more");
+    if (c->sticky) return c->sticky;
+    std::vector<vx_merkle_tree_tile> tiles(plan.n_tiles);
+    std::vector<uint64_t> off((size_t)n_layers + 1);
+    (void)vx_merkle::plan_trees(counts, n_layers, &plan, tiles.data(), tiles.size(), off.data());
+    // hashes | tree | tiles: every part a multiple of 16 bytes
+    const uint64_t o_tree = plan.rows * 32, o_tiles = o_tree + plan.tree_rows * 32;
+    CallBufs b;
+    int rc = b.make(c, o_tiles + (uint64_t)plan.n_tiles * sizeof(vx_merkle_tree_tile), who);
+    if (rc) return rc;
+    VX_HIP(hipMemcpyAsync(b.d, hashes, plan.rows * 32, hipMemcpyHostToDevice, b.stream));
+    VX_HIP(hipMemcpyAsync(b.d + o_tiles, tiles.data(), tiles.size() * sizeof(vx_merkle_tree_tile),
+                          hipMemcpyHostToDevice, b.stream));
+    rc = vx_merkle_device_trees(b.d, &plan, reinterpret_cast<const vx_merkle_tree_tile*>(b.d + o_tiles), height,
+                                b.d + o_tree, b.stream);
+    if (rc) return rc;
+    VX_HIP(hipMemcpyAsync(tree_out, b.d + o_tree, plan.tree_rows * 32, hipMemcpyDeviceToHost, b.stream));
+    VX_HIP(hipStreamSynchronize(b.stream));
+    if (roots_out)
+        for (uint32_t f = 0; f < n_layers; ++f) std::memcpy(roots_out + (size_t)f * 32, tree_out + (off[f + 1] - 1) * 32, 32);
+    return 0;
+}
+
+int vx_merkle_tree_proof(const uint8_t* tree, uint32_t m, uint32_t height, uint32_t level, uint64_t pos,
+                         uint32_t span, uint32_t uncles, uint8_t* out) {
+    if (!tree || !out) return fail(VX_EINVAL, "vx_merkle_tree_proof: NULL tree or out");
+    // pad(0..): made once, 169 hashes (the lookup itself hashes nothing)
+    static const std::vector<uint8_t> pads = [] {
+        std::vector<uint8_t> p((size_t)vx_merkle::kProofPads * 32, 0);
+        for (uint32_t h = 1; h < vx_merkle::kProofPads; ++h)
+            host_sha256_pair(p.data() + (size_t)(h - 1) * 32, p.data() + (size_t)(h - 1) * 32, p.data() + (size_t)h * 32);
+        return p;
+    }();
+    if (vx_merkle::tree_proof(tree, m, height, level, pos, span, uncles, pads.data(), out))
+        return fail(VX_EINVAL,
+                    "vx_merkle_tree_proof: m == 0, height > 64, span not a power of two in 1..512, uncles > 64, "
+                    "level > K, or a span past the level's rows");
+    return 0;
+}
+
+int64_t vx_merkle_tree_layout(const uint64_t* file_lengths, size_t nfiles, uint32_t piece_length,
+                              uint32_t* counts_out, uint64_t* tree_off_out) {
+    if (nfiles && !file_lengths) return fail(VX_EINVAL, "vx_merkle_tree_layout: NULL file_lengths");
+    if (piece_length < VX_MERKLE_BLOCK || (piece_length & (piece_length - 1)))
+        return fail(VX_EINVAL, "vx_merkle_tree_layout: piece_length must be a power of two >= 16384");
+    const int64_t rows = vx_merkle::tree_layout(file_lengths, nfiles, piece_length, counts_out, tree_off_out);
+    if (rows < 0) return fail(VX_EINVAL, "vx_merkle_tree_layout: a file has 2^32 pieces or more");
+    return rows;
+}
+
+int64_t vx_merkle_hash_files_range(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                                   uint32_t piece_length, size_t n_pieces, size_t first, size_t count,
+                                   uint8_t* rows_out, uint8_t* ok_out, uint32_t io_threads) {
+    if (!rows_out) return fail(VX_EINVAL, "vx_merkle_hash_files: NULL rows_out");
+    return merkle_files_impl(c, paths, file_lengths, nfiles, piece_length, nullptr, n_pieces, first, count, ok_out,
+                             io_threads, rows_out);
+}
+
+int64_t vx_merkle_hash_files(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                             uint32_t piece_length, size_t n_pieces, uint8_t* rows_out, uint8_t* ok_out,
+                             uint8_t* tree_out, uint64_t tree_rows, uint32_t io_threads) {
+    if (!rows_out) return fail(VX_EINVAL, "vx_merkle_hash_files: NULL rows_out");
+    return merkle_files_impl(c, paths, file_lengths, nfiles, piece_length, nullptr, n_pieces, 0, n_pieces, ok_out,
+                             io_threads, rows_out, tree_out, tree_rows);
 }
 
 int64_t vx_merkle_verify_files_range(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,

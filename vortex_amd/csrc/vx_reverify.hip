@@ -122,7 +122,7 @@ int verify_chunked(FileVerify& fv, vx_files::Readers& rd, uint64_t n, uint32_t p
     const uint64_t last_len = total - (n - 1) * (uint64_t)pl;
     const uint64_t cnt = end - first;
     ChunkPipe cp(c);
-    int rc = cp.open(cnt, fv.expected + 20 * first, "vx_verify_files");
+    int rc = cp.open(cnt, fv.digests_out ? nullptr : fv.expected + 20 * first, "vx_verify_files");
     if (!rc && c->verify_copy_stream) rc = cp.use_copy_stream();
     cp.bytes = cnt * (uint64_t)pl - (end == n ? (uint64_t)pl - last_len : 0);
     // windows of W pieces; each window runs its rounds in order
@@ -204,9 +204,9 @@ int verify_chunked(FileVerify& fv, vx_files::Readers& rd, uint64_t n, uint32_t p
     }
     rd.wait();  // error path: no read may still target a stage
     release_filling_slots(c);  // rounds read but never launched (error path)
-    rc = cp.finish(fv.matched_out, nullptr, rc, fv.bad.data());
+    rc = cp.finish(fv.digests_out ? nullptr : fv.matched_out, fv.digests_out, rc, fv.bad.data());
     tlm.fold(rc);
-    if (!rc)
+    if (!rc && !fv.digests_out)
         for (uint64_t i = 0; i < cnt; ++i)
             if (fv.bad[i]) fv.matched_out[i] = 0;
     fv.done = cnt;
@@ -221,9 +221,13 @@ namespace vxe {
 // (vx_verify_files_split: pieces [sp->first, sp->end), always chunk rounds).
 int64_t verify_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
                           uint32_t piece_length, const uint8_t* expected, size_t n_pieces, size_t first,
-                          size_t count, uint8_t* matched_out, uint32_t io_threads, vx_split* sp) {
-    if (!c || (nfiles && (!paths || !file_lengths)) || piece_length == 0 || (n_pieces && !expected) ||
-        (count && !matched_out))
+                          size_t count, uint8_t* matched_out, uint32_t io_threads, vx_split* sp,
+                          uint8_t* digests_out) {
+    // digests_out set: vx_hash_files.  No expected table, always chunk rounds
+    // (ChunkPipe keeps the digests), matched_out is the call's ok_out (may be NULL).
+    const bool hashing = digests_out != nullptr;
+    if (!c || (nfiles && (!paths || !file_lengths)) || piece_length == 0 ||
+        (!hashing && ((n_pieces && !expected) || (count && !matched_out))))
         return fail(VX_EINVAL, "vx_verify_files: bad argument");
     if (first > n_pieces || count > n_pieces - first)
         return fail(VX_EINVAL, "vx_verify_files: piece range outside the torrent");
@@ -235,7 +239,7 @@ int64_t verify_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
         return fail(VX_EINVAL, "vx_verify_files: n_pieces does not match the files' total length");
     if (count == 0) return 0;
     const uint64_t C = verify_chunk_for(c, count);
-    bool chunked = piece_length >= 2 * C || sp;  // the split always streams chunk rounds
+    bool chunked = piece_length >= 2 * C || sp || hashing;  // the split and the hash call always stream chunk rounds
     if (piece_length > c->cfg.max_piece_len) chunked = true;  // whole pieces would not fit a slot
     if (chunked ? c->slots[0].arena_cap < std::min<uint64_t>(C, align_up(piece_length, vx_files::DirectIo::kBlock))
                 : piece_length > c->cfg.max_piece_len)
@@ -253,11 +257,12 @@ int64_t verify_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
     for (size_t f = 0; f < nfiles; ++f) fds[f] = open(paths[f], O_RDONLY | O_CLOEXEC);
     const int nthreads = io_threads ? (int)io_threads : (int)std::max(1u, std::min(16u, usable_cpus()));
     std::vector<uint8_t> bad(count, 0);
-    if (!sp) std::memset(matched_out, 0, count);  // (the split's pool writes its entries concurrently)
+    if (!sp && matched_out) std::memset(matched_out, 0, count);  // (the split's pool writes its entries concurrently)
     {
         const vx_files::DirectIo dio(fds, c->cfg.direct_io != 0);
         vx_files::Readers rd(nthreads, fs, fds, piece_length, bad.data(), first, &dio);
         FileVerify fv{c, expected, matched_out, bad};
+        fv.digests_out = digests_out;
         c->harvest_counts_mismatches = false;
         // Uncached data: the disk binds, and takes bigger reads better.
         const uint64_t Cc = c->cfg.verify_cold_chunk;
@@ -290,6 +295,10 @@ int64_t verify_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
             // abandoned pieces never reach vx_stats.
             wait_and_free_inflight(c);
             c->done.clear();
+        }
+        for (size_t i = 0; i < count && hashing && !rc; ++i) {  // never a digest over bytes that were not read
+            if (matched_out) matched_out[i] = !bad[i];
+            if (bad[i]) std::memset(digests_out + i * 20, 0, 20);
         }
     }
     return end_files_call(c, fds, bad, t_call, rc);
@@ -341,6 +350,30 @@ int64_t vx_verify_files_range(vx_ctx* c, const char* const* paths, const uint64_
                               size_t count, uint8_t* matched_out, uint32_t io_threads) {
     return verify_files_impl(c, paths, file_lengths, nfiles, piece_length, expected, n_pieces, first, count,
                              matched_out, io_threads, nullptr);
+}
+
+int64_t vx_hash_files_range(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                            uint32_t piece_length, size_t n_pieces, size_t first, size_t count, uint8_t* digests_out,
+                            uint8_t* ok_out, uint32_t io_threads) {
+    // (what needs no context first, as the other hash calls)
+    if (!c) return fail(VX_EINVAL, "vx_hash_files: NULL context");
+    if ((nfiles && (!paths || !file_lengths)) || piece_length == 0 || !digests_out)
+        return fail(VX_EINVAL, "vx_hash_files: NULL paths/file_lengths/digests_out, or piece_length 0");
+    uint64_t total = 0;
+    for (size_t f = 0; f < nfiles; ++f) total += file_lengths[f];
+    if (n_pieces != (total + piece_length - 1) / piece_length)
+        return fail(VX_EINVAL, "vx_hash_files: n_pieces does not match the files' total length");
+    if (first > n_pieces || count > n_pieces - first)
+        return fail(VX_EINVAL, "vx_hash_files: piece range outside the torrent");
+    return verify_files_impl(c, paths, file_lengths, nfiles, piece_length, nullptr, n_pieces, first, count, ok_out,
+                             io_threads, nullptr, digests_out);
+}
+
+int64_t vx_hash_files(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+                      uint32_t piece_length, size_t n_pieces, uint8_t* digests_out, uint8_t* ok_out,
+                      uint32_t io_threads) {
+    return vx_hash_files_range(c, paths, file_lengths, nfiles, piece_length, n_pieces, 0, n_pieces, digests_out, ok_out,
+                               io_threads);
 }
 
 int64_t vx_verify_files(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,

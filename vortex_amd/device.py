@@ -594,6 +594,52 @@ def merkle_layers(hashes: torch.Tensor, counts, height: int, expected: Optional[
     return roots, matched
 
 
+def merkle_trees(hashes: torch.Tensor, counts, height: int, tree: Optional[torch.Tensor] = None,
+                 stream: Optional[torch.cuda.Stream] = None):
+    """The trees of many layers in one call (vx_merkle_device_trees): `hashes`
+    and `counts` as for :func:`merkle_layers`; every level of every layer's
+    tree is kept (merkle.build_tree is the model), the trees back to back.
+    Returns (tree, tree_off): tree is [sum(merkle.tree_rows(c)),32] uint8 on the
+    hashes' device (None allocates it), tree_off a host list of n + 1 row
+    offsets; the root of layer f is row tree_off[f + 1] - 1.  One launch per
+    pass (at most 4).  Enqueue-only but for the upload of the tiles."""
+    import ctypes
+
+    from . import _lib
+
+    _req(hashes, "hashes")
+    dev = hashes.device
+    n = len(counts)
+    host_counts = [int(c) for c in counts]
+    if any(not 0 <= c < 1 << 32 for c in host_counts):
+        raise ValueError("merkle_trees: a count is outside 0..2^32-1")
+    carr = (ctypes.c_uint32 * max(n, 1))(*host_counts)
+    if not 0 <= height <= 64:
+        raise ValueError("merkle_trees: height must be 0..64")
+    plan = _lib.vx_merkle_tree_plan()
+    off = (ctypes.c_uint64 * (n + 1))()
+    check(lib().vx_merkle_tree_plan(carr, n, ctypes.byref(plan), None, 0, off), "vx_merkle_tree_plan")
+    if hashes.numel() != 32 * plan.rows:
+        raise ValueError(f"hashes must hold sum(counts) = {plan.rows} rows of 32 bytes")
+    if tree is None:
+        tree = torch.empty((int(plan.tree_rows), 32), dtype=torch.uint8, device=dev)
+    else:
+        _req(tree, "tree")
+        if tree.numel() < 32 * plan.tree_rows or tree.device != dev:
+            raise ValueError(f"tree must hold {plan.tree_rows} rows of 32 bytes on the hashes' device")
+    if n == 0:
+        return tree, list(off)
+    tiles = (_lib.vx_merkle_tree_tile * plan.n_tiles)()
+    check(lib().vx_merkle_tree_plan(carr, n, ctypes.byref(plan), tiles, plan.n_tiles, off), "vx_merkle_tree_plan")
+    d_tiles = _upload(tiles, dev, stream)
+    if stream is not None:  # the tiles outlive this call on the stream that uses them
+        d_tiles.record_stream(stream)
+    rc = lib().vx_merkle_device_trees(hashes.data_ptr(), ctypes.byref(plan), d_tiles.data_ptr(), height,
+                                      tree.data_ptr(), _stream_ptr(stream, dev))
+    check(rc, "vx_merkle_device_trees")
+    return tree, list(off)
+
+
 def check_proofs(proofs, n_rows: int, n_expected: int):
     """A host sequence of proofs, each (pos, row, expected, span, uncles) or a
     ``vx_merkle_proof``, as a ctypes array after the checks of

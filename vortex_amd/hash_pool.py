@@ -633,6 +633,120 @@ class HashPool:
         check(rc, "vx_hybrid_verify_files", self.lib)
         return [(bool(b & 1), bool(b & 2)) for b in out.raw[:count]]
 
+    # ---- creating a torrent: the tables the verify calls take, made from the files ----
+
+    def hash_files(self, paths: Sequence[str], file_lengths: Sequence[int], piece_length: int, io_threads: int = 0,
+                   first: int = 0, count: int | None = None) -> tuple[bytes, list[bool], int]:
+        """A v1 torrent's `pieces` string from its files (vx_hash_files): the
+        layout of verify_files, the SHA-1 of every piece.  Returns (digests,
+        ok, pieces with I/O errors): count * 20 bytes, and ok[i] False (its
+        digest all zero) where a byte of the piece could not be read.
+        first/count restrict the call to pieces [first, first+count)."""
+        n = (sum(file_lengths) + piece_length - 1) // piece_length if piece_length > 0 else 0
+        if count is None:
+            count = n - first
+        arr, lens = _path_arrays(paths, file_lengths)
+        dig = ctypes.create_string_buffer(20 * max(1, count))
+        ok = ctypes.create_string_buffer(max(1, count))
+        if first == 0 and count == n:
+            rc = self.lib.vx_hash_files(self._h, arr, lens, len(paths), piece_length, n, dig, ok, io_threads)
+        else:
+            rc = self.lib.vx_hash_files_range(self._h, arr, lens, len(paths), piece_length, n, first, count, dig, ok,
+                                              io_threads)
+        bad = check(rc, "vx_hash_files", self.lib)
+        return dig.raw[:20 * count], [bool(b) for b in ok.raw[:count]], int(bad)
+
+    def hash_merkle_files(self, paths: Sequence[str], file_lengths: Sequence[int], piece_length: int,
+                          io_threads: int = 0, first: int = 0, count: int | None = None,
+                          trees: bool = True) -> tuple[bytes, list[bool], Optional[bytes], int]:
+        """A v2 torrent's hashes from its files (vx_merkle_hash_files).
+        Returns (rows, ok, tree, pieces with I/O errors): rows is what
+        verify_merkle_files takes as `expected` (32 bytes per piece); tree
+        holds every non-empty file's layer tree, laid out by
+        merkle.tree_layout: the last row of a file's tree is its `pieces
+        root`, its first rows are its `piece layers` entry, and the levels
+        between answer hash requests (merkle.proof_from_tree).  A piece that
+        could not be read has ok False and a zero row, and its file a zero
+        tree.  A range call (first/count) or trees=False returns tree None."""
+        n = len(merkle.torrent_pieces(file_lengths, piece_length)[0])
+        if count is None:
+            count = n - first
+        arr, lens = _path_arrays(paths, file_lengths)
+        rows = ctypes.create_string_buffer(32 * max(1, count))
+        ok = ctypes.create_string_buffer(max(1, count))
+        tree = None
+        if first == 0 and count == n:
+            tree_rows = merkle.tree_layout(file_lengths, piece_length)[1][-1] if trees else 0
+            tree = ctypes.create_string_buffer(32 * max(1, tree_rows)) if trees else None
+            rc = self.lib.vx_merkle_hash_files(self._h, arr, lens, len(paths), piece_length, n, rows, ok, tree,
+                                               tree_rows, io_threads)
+        else:
+            rc = self.lib.vx_merkle_hash_files_range(self._h, arr, lens, len(paths), piece_length, n, first, count,
+                                                     rows, ok, io_threads)
+        bad = check(rc, "vx_merkle_hash_files", self.lib)
+        return (rows.raw[:32 * count], [bool(b) for b in ok.raw[:count]],
+                tree.raw[:32 * tree_rows] if tree is not None else None, int(bad))
+
+    def hash_hybrid_files(self, paths: Sequence[str], file_lengths: Sequence[int], piece_length: int,
+                          io_threads: int = 0, first: int = 0, count: int | None = None,
+                          trees: bool = True) -> tuple[bytes, bytes, list[bool], Optional[bytes], int]:
+        """A hybrid torrent's hashes from its files in one pass
+        (vx_hybrid_hash_files): (pieces, rows, ok, tree, pieces with I/O
+        errors).  `pieces` is the v1 table over data plus implied pad zeros, as
+        verify_hybrid_files takes it; rows, ok and tree as hash_merkle_files."""
+        n = len(merkle.torrent_pieces(file_lengths, piece_length)[0])
+        if count is None:
+            count = n - first
+        arr, lens = _path_arrays(paths, file_lengths)
+        sha1 = ctypes.create_string_buffer(20 * max(1, count))
+        rows = ctypes.create_string_buffer(32 * max(1, count))
+        ok = ctypes.create_string_buffer(max(1, count))
+        tree = None
+        if first == 0 and count == n:
+            tree_rows = merkle.tree_layout(file_lengths, piece_length)[1][-1] if trees else 0
+            tree = ctypes.create_string_buffer(32 * max(1, tree_rows)) if trees else None
+            rc = self.lib.vx_hybrid_hash_files(self._h, arr, lens, len(paths), piece_length, n, sha1, rows, ok, tree,
+                                               tree_rows, io_threads)
+        else:
+            rc = self.lib.vx_hybrid_hash_files_range(self._h, arr, lens, len(paths), piece_length, n, first, count,
+                                                     sha1, rows, ok, io_threads)
+        bad = check(rc, "vx_hybrid_hash_files", self.lib)
+        return (sha1.raw[:20 * count], rows.raw[:32 * count], [bool(b) for b in ok.raw[:count]],
+                tree.raw[:32 * tree_rows] if tree is not None else None, int(bad))
+
+    def build_piece_trees(self, layers: Sequence[bytes], piece_length: int) -> tuple[list[bytes], list[bytes]]:
+        """The trees of a v2 torrent's `piece layers` (vx_merkle_build_trees),
+        for a client that has the layers from a .torrent and starts seeding:
+        layers[f] is one file's string of 32-byte piece hashes.  Returns
+        (trees, roots): trees[f] is merkle.build_tree(layers[f], height) with
+        height = log2(piece_length / 16 KiB), roots[f] its last row.  Works
+        while async pieces are pending and leaves stats() alone."""
+        n = len(layers)
+        if any(len(x) == 0 or len(x) % 32 for x in layers):
+            raise ValueError("a layer is a non-empty string of 32-byte hashes")
+        height = merkle.log2_width(piece_length)
+        blob = b"".join(bytes(x) for x in layers)
+        hashes = ctypes.create_string_buffer(blob, max(1, len(blob)))
+        counts = [len(x) // 32 for x in layers]
+        carr = (ctypes.c_uint32 * max(n, 1))(*counts)
+        off = [0]
+        for c in counts:
+            off.append(off[-1] + merkle.tree_rows(c))
+        tree = ctypes.create_string_buffer(32 * max(1, off[-1]))
+        roots = ctypes.create_string_buffer(32 * max(1, n))
+        check(self.lib.vx_merkle_build_trees(self._h, hashes, carr, n, height, tree, roots),
+              "vx_merkle_build_trees", self.lib)
+        view, raw = memoryview(tree), roots.raw
+        return ([bytes(view[32 * off[f]:32 * off[f + 1]]) for f in range(n)],
+                [raw[32 * f:32 * f + 32] for f in range(n)])
+
+
+def _path_arrays(paths: Sequence[str], file_lengths: Sequence[int]):
+    """A files call's paths and lengths as ctypes arrays."""
+    arr = (ctypes.c_char_p * max(1, len(paths)))(*[os.fsencode(p) for p in paths])
+    lens = (ctypes.c_uint64 * max(1, len(file_lengths)))(*file_lengths)
+    return arr, lens
+
 
 def _verify_files(pool: "HashPool", paths: Sequence[str], file_lengths: Sequence[int], piece_length: int,
                   expected: bytes, io_threads: int = 0, first: int = 0,

@@ -138,6 +138,66 @@ def layer_root(hashes, height: int = 0) -> bytes:
     return _Tree(rows, height).node((len(rows) - 1).bit_length(), 0)
 
 
+def tree_rows(m: int) -> int:
+    """Rows of the tree of an m-row layer (vx_merkle_tree_rows): level k holds
+    ceil(m / 2^k) rows, k = 0..ceil(log2 m); 0 for m = 0."""
+    if m < 0:
+        raise ValueError("m must be >= 0")
+    if m == 0:
+        return 0
+    return sum((m + (1 << k) - 1) >> k for k in range((m - 1).bit_length() + 1))
+
+
+def tree_layout(file_lengths, piece_length: int) -> tuple[list[int], list[int]]:
+    """(counts, tree_off) of a torrent's trees (vx_merkle_tree_layout): per file
+    the rows of its layer (0: empty, 1: at most piece_length bytes, the row is
+    its `pieces root`; else its piece count) and len(file_lengths) + 1 row
+    offsets; file f's tree is rows [tree_off[f], tree_off[f + 1])."""
+    log2_width(piece_length)
+    counts = [(int(length) + piece_length - 1) // piece_length for length in file_lengths]
+    off = [0]
+    for c in counts:
+        off.append(off[-1] + tree_rows(c))
+    return counts, off
+
+
+def build_tree(rows, height: int = 0) -> bytes:
+    """The tree of a layer of m >= 1 hashes standing `height` levels above the
+    leaves, with hashlib: every level k = 0..ceil(log2 m), level k the
+    ceil(m / 2^k) nodes of the BEP 52 tree that cover a row of the layer (node
+    (k, j) of :class:`_Tree`), level 0 first; tree_rows(m) * 32 bytes, the last
+    row the layer's root.  The model of vx_merkle_device_trees."""
+    level = _rows(rows)
+    if not level:
+        raise ValueError("a layer holds at least one hash")
+    out = [b"".join(level)]
+    k = 0
+    while len(level) > 1:
+        if len(level) & 1:
+            level = level + [pad_hash(height + k)]
+        level = [hashlib.sha256(level[j] + level[j + 1]).digest() for j in range(0, len(level), 2)]
+        out.append(b"".join(level))
+        k += 1
+    return b"".join(out)
+
+
+def proof_from_tree(tree: bytes, m: int, height: int, level: int, pos: int, span: int, uncles: int) -> bytes:
+    """:func:`make_proof` over level `level` of a layer whose tree is at hand
+    (vx_merkle_tree_proof): a lookup that hashes nothing.  Equal to
+    make_proof(rows of that level, height + level, pos, span, uncles)."""
+    import ctypes
+
+    from ._lib import check, lib
+
+    if len(tree) != 32 * tree_rows(m):
+        raise ValueError("tree must hold tree_rows(m) rows of 32 bytes")
+    if min(level, pos, span, uncles, height) < 0:
+        raise ValueError("level, pos, span, uncles and height must be >= 0")
+    out = ctypes.create_string_buffer(32 * (span + uncles) or 1)
+    check(lib().vx_merkle_tree_proof(bytes(tree), m, height, level, pos, span, uncles, out), "vx_merkle_tree_proof")
+    return out.raw[:32 * (span + uncles)]
+
+
 def make_proof(layer, height: int, pos: int, span: int, uncles: int) -> bytes:
     """The rows a seeder sends in a `hashes` message for span number `pos` of
     `span` hashes (a power of two) of `layer`: the span's rows
