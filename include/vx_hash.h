@@ -863,6 +863,57 @@ int vx_merkle_verify_proofs(vx_ctx* ctx, const uint8_t* hashes, uint64_t n_rows,
                             uint32_t n, const uint8_t* expected, uint32_t n_expected, uint8_t* matched_out,
                             uint8_t* tops_out);
 
+/* ---- Block checks: which 16 KiB blocks of a v2 piece are wrong -----------
+ * A piece whose root is wrong says nothing about its blocks.  A client that
+ * has the piece's leaf hashes (a `hashes` request at base layer 0, proven
+ * against the piece-layer row it trusts with vx_merkle_verify_proofs) compares
+ * every block with its leaf here and re-requests only the bad ones.  The same
+ * calls return the leaf rows themselves: what a seeder answers such a request
+ * from.
+ *
+ * The bitmap, a fixed contract: uint64 words, wpp = max(1, W / 64) words per
+ * piece with W = 2^log2_width leaf slots; block b of piece i is bit b & 63 of
+ * word i * wpp + (b >> 6); a set bit is a block whose SHA-256 differs from its
+ * expected row.  A slot at or past the piece's end is never set, whatever its
+ * expected row holds, and the bits of a word above W are 0.  Every word of
+ * every piece is written, zeros included: the caller never clears it. */
+/* Words of the bitmap of n pieces: n * max(1, 2^log2_width / 64); host only.
+ * 0 when log2_width > VX_MERKLE_MAX_LOG2_WIDTH. */
+uint64_t vx_merkle_bitmap_words(uint32_t n, uint32_t log2_width);
+/* The batch of vx_merkle_device_ragged (every piece a tree of 2^log2_width
+ * slots), checked block by block: leaf g = (i << log2_width) + b is compared
+ * with row g of d_expected_leaves ((n << log2_width) * 32 bytes) into d_bad
+ * (vx_merkle_bitmap_words(n, log2_width) words).  d_leaves_out (may be NULL)
+ * gets the (n << log2_width) * 32 bytes vx_merkle_device_ragged writes to
+ * d_leaves.  d_expected_leaves and d_bad are given together or both NULL (then
+ * the call only writes d_leaves_out; all three NULL is VX_EINVAL).  d_base,
+ * d_expected_leaves and d_leaves_out 16-byte, d_bad 8-byte aligned; n <<
+ * log2_width fits 32 bits.  One launch, no atomics.  The device-resident
+ * metadata is not checked here; vortex_amd.device.merkle_block_check checks
+ * it.  Enqueue-only; n == 0 launches nothing. */
+int vx_merkle_device_block_check(const void* d_base, const uint64_t* d_offsets, const uint32_t* d_lens, uint32_t n,
+                                 uint32_t log2_width, const void* d_expected_leaves, uint64_t* d_bad,
+                                 void* d_leaves_out, void* stream);
+/* The same on a context, for pieces in host memory (plain or registered):
+ * piece i is ptrs[i], lens[i] bytes, a tree of W = piece_length /
+ * VX_MERKLE_BLOCK slots.  expected_leaves (may be NULL): n * W rows of 32
+ * bytes, piece i's at row i * W; bad_out: vx_merkle_bitmap_words(n,
+ * log2(W)) words, required iff expected_leaves is given; bad_counts_out (may
+ * be NULL, needs expected_leaves): per piece the number of set bits;
+ * leaves_out (may be NULL): n * W * 32 bytes.  With expected_leaves and
+ * leaves_out both NULL the call is VX_EINVAL.  piece_length is a power of two, VX_MERKLE_BLOCK <=
+ * piece_length <= max_piece_len (VX_ERANGE above), lens[i] <= piece_length, no
+ * NULL pointer for a non-empty piece; all of it is checked before anything is
+ * allocated or copied.  Synchronous, on a stream and a device block of its
+ * own as vx_merkle_verify_layers: the pieces go in rounds of at most
+ * slot_bytes, copied from where they lie, one wait per round.  It touches
+ * neither the batch slots, the pending count nor vx_get_stats and does not
+ * return VX_EBUSY: a block check follows a failed piece in the middle of a
+ * download, while async pieces are pending.  n == 0 returns 0. */
+int vx_merkle_check_blocks(vx_ctx* ctx, const uint8_t* const* ptrs, const uint32_t* lens, size_t n,
+                           uint32_t piece_length, const uint8_t* expected_leaves, uint64_t* bad_out,
+                           uint32_t* bad_counts_out, uint8_t* leaves_out);
+
 /* ---- Hashing: from files to `pieces`, `piece layers` and `pieces root` ---
  * Every entry above checks hashes that somebody else made.  The entries below
  * make them: what a client needs to create a torrent from a directory, and what
@@ -934,7 +985,9 @@ int vx_merkle_build_trees(vx_ctx* ctx, const uint8_t* hashes, const uint32_t* co
  * n_k, or of a level above K, is the pad hash of its height.  VX_EINVAL: span
  * not a power of two in 1..512, uncles > 64, level > K, height > 64, m == 0, or
  * pos * span >= n_level (a span without a row of the level).  Proofs at the
- * 16 KiB leaf level need the leaf layer, which the calls below do not keep. */
+ * 16 KiB leaf level need the leaf layer, which the hash calls below do not
+ * keep: vx_merkle_check_blocks with leaves_out returns a piece's, and its tree
+ * (vx_merkle_build_trees at height 0) serves the rows inside the piece. */
 int vx_merkle_tree_proof(const uint8_t* tree, uint32_t m, uint32_t height, uint32_t level, uint64_t pos,
                          uint32_t span, uint32_t uncles, uint8_t* out);
 

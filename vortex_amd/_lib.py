@@ -56,6 +56,7 @@ EXPORTS = (
     "vx_merkle_device_pieces", "vx_merkle_submit", "vx_merkle_poll",
     "vx_merkle_layers_plan", "vx_merkle_device_layers", "vx_merkle_device_proofs", "vx_merkle_verify_layers",
     "vx_merkle_verify_proofs",
+    "vx_merkle_bitmap_words", "vx_merkle_device_block_check", "vx_merkle_check_blocks",
     "vx_hybrid_device_pieces", "vx_hybrid_verify_files", "vx_hybrid_verify_files_range",
     "vx_hybrid_submit", "vx_hybrid_set_piece_tables", "vx_hybrid_submit_piece", "vx_hybrid_poll",
     "vx_merkle_tree_rows", "vx_merkle_tree_plan", "vx_merkle_device_trees", "vx_merkle_build_trees",
@@ -280,6 +281,9 @@ def _declare(L: ctypes.CDLL, tuning: bool = False) -> None:
         "vx_merkle_device_proofs": ([vp, vp, c.c_uint32, vp, vp, vp, vp], c.c_int),
         "vx_merkle_verify_layers": ([vp, vp, vp, c.c_uint32, c.c_uint32, vp, vp, vp], c.c_int),
         "vx_merkle_verify_proofs": ([vp, vp, c.c_uint64, vp, c.c_uint32, vp, c.c_uint32, vp, vp], c.c_int),
+        "vx_merkle_bitmap_words": ([c.c_uint32, c.c_uint32], c.c_uint64),
+        "vx_merkle_device_block_check": ([vp, vp, vp, c.c_uint32, c.c_uint32, vp, vp, vp, vp], c.c_int),
+        "vx_merkle_check_blocks": ([vp, vp, vp, c.c_size_t, c.c_uint32, vp, vp, vp, vp], c.c_int),
         "vx_hybrid_device_pieces": ([vp, vp, vp, vp, vp, c.c_uint32, c.c_uint32, vp, vp, vp, vp, vp, vp, vp], c.c_int),
         "vx_hybrid_verify_files": ([vp, vp, vp, c.c_size_t, c.c_uint32, vp, vp, c.c_size_t, vp, c.c_uint32],
                                    c.c_int64),

@@ -30,6 +30,9 @@
 //    workgroup's 256 leaf rows stay in LDS and are reduced there; trees of at
 //    most 256 leaves finish in the one launch, wider ones leave a top per
 //    256-leaf tile for the node kernel.  No leaf layer is kept.
+//  * block check kernel (vx_merkle_device_block_check): the leaf kernel's
+//    lanes, each comparing its leaf with an expected row; a wave's verdicts
+//    leave as one ballot, a bit per 16 KiB block.
 #include <hip/hip_runtime.h>
 
 #include <stddef.h>
@@ -163,6 +166,70 @@ __global__ __launch_bounds__(kBlock) void merkle_leaf_kernel(const uint8_t* __re
         for (int k = 0; k < 8; ++k) s.h[k] = 0;  // beyond the piece: the zero hash, not a hash of anything
     }
     if (g < rows) store_row(leaves, g, s);
+}
+
+// Block check (vx_merkle_device_block_check, DESIGN.md §3.7 "Block checks"):
+// the lanes and the streaming of merkle_leaf_kernel<true>, but each lane
+// compares its digest with row g of expected_leaves and a wave's verdicts
+// leave as one ballot.  Bitmap: uint64 words, max(1, W/64) per piece, block b
+// of piece i = bit b & 63 of word i * wpp + (b >> 6).
+//  * W >= 64: a wave is 64 consecutive slots of one piece, its ballot is one
+//    whole word; lane 0 stores it.
+//  * W < 64: a wave holds 64 / W whole pieces; the lane of each piece's slot 0
+//    shifts the ballot down to its own bit and stores the piece's W bits.
+// Every word has exactly one writing lane (no atomics, no LDS) and every word
+// of pieces [0, n) is written, zeros included.  A slot at or past the piece's
+// end is never bad.  The expected row is loaded after the hashing: it is not
+// live across the streaming loop.  expected_leaves NULL: leaves_out only.
+__global__ __launch_bounds__(kBlock) void merkle_block_check_kernel(const uint8_t* __restrict__ base,
+                                                                    const uint64_t* __restrict__ offsets,
+                                                                    const uint32_t* __restrict__ lens, uint32_t n,
+                                                                    uint32_t log2_width,
+                                                                    const uint8_t* __restrict__ expected_leaves,
+                                                                    unsigned long long* __restrict__ bad_words,
+                                                                    uint8_t* __restrict__ leaves_out) {
+    const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t rows = n << log2_width;
+    // Lanes past the last row redo row rows-1 (in bounds, the wave stays
+    // convergent), store nothing and contribute 0 to the ballot.
+    const uint32_t gg = g < rows ? g : rows - 1;
+    const uint32_t piece = gg >> log2_width;
+    const uint32_t slot = gg & ((1u << log2_width) - 1);
+    const uint32_t plen = lens[piece];
+    const uint8_t* p = base + offsets[piece];
+    const uint64_t start = (uint64_t)slot * kLeaf;
+    const uint32_t leaf_len = start < plen ? (plen - start < kLeaf ? (uint32_t)(plen - start) : kLeaf) : 0;
+    const uint32_t ng = leaf_len >> 7;
+    const uint32_t ng_wave = __builtin_amdgcn_readfirstlane(wave_max(ng));
+    p += start < plen ? start : 0;
+    State s = sha256::iv();
+    stream_groups(s, reinterpret_cast<const uint4*>(p), ng, ng_wave);
+    if (leaf_len == kLeaf) {
+        sha256::compress_const(s, kPadLeaf);
+    } else if (leaf_len) {
+        finish_tail(s, p + (size_t)ng * 128, leaf_len & 127u, leaf_len);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s.h[k] = 0;  // beyond the piece: the zero hash, not a hash of anything
+    }
+    if (leaves_out && g < rows) store_row(leaves_out, g, s);
+    if (!expected_leaves) return;  // (kernel-uniform)
+    asm volatile("" ::: "memory");  // the row's loads stay below the hashing
+    const uint4* x = reinterpret_cast<const uint4*>(expected_leaves + (size_t)gg * 32);
+    const uint4 x0 = x[0], x1 = x[1];
+    const uint32_t diff = (x0.x ^ sha256::bswap(s.h[0])) | (x0.y ^ sha256::bswap(s.h[1])) |
+                          (x0.z ^ sha256::bswap(s.h[2])) | (x0.w ^ sha256::bswap(s.h[3])) |
+                          (x1.x ^ sha256::bswap(s.h[4])) | (x1.y ^ sha256::bswap(s.h[5])) |
+                          (x1.z ^ sha256::bswap(s.h[6])) | (x1.w ^ sha256::bswap(s.h[7]));
+    const bool bad = g < rows && start < plen && diff != 0;
+    const unsigned long long mask = __ballot(bad);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (log2_width >= 6) {
+        // (rows is a multiple of 64: g < rows is wave-uniform)
+        if (lane == 0 && g < rows) bad_words[((size_t)piece << (log2_width - 6)) + (slot >> 6)] = mask;
+    } else if (slot == 0 && g < rows) {
+        bad_words[piece] = (mask >> lane) & ((1ull << (1u << log2_width)) - 1);
+    }
 }
 
 // Block stream (the re-verify from disk): lane b hashes stage
@@ -722,6 +789,16 @@ hipError_t launch_merkle_pieces(const uint8_t* base, const uint64_t* offsets, co
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !wide) return e;
     return launch_nodes(n, top_width, work, log2w_top, roots, expected, matched, stream);
+}
+
+hipError_t launch_merkle_block_check(const uint8_t* base, const uint64_t* offsets, const uint32_t* lens, uint32_t n,
+                                     uint32_t log2_width, const uint8_t* expected_leaves, uint64_t* bad,
+                                     uint8_t* leaves_out, hipStream_t stream) {
+    const uint64_t rows = (uint64_t)n << log2_width;
+    const uint32_t grid = (uint32_t)((rows + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(merkle_block_check_kernel, dim3(grid), dim3(kBlock), 0, stream, base, offsets, lens, n,
+                       log2_width, expected_leaves, reinterpret_cast<unsigned long long*>(bad), leaves_out);
+    return hipGetLastError();
 }
 
 hipError_t launch_merkle_blocks(const uint8_t* stage, const uint32_t* rows, const uint32_t* lens, uint32_t n_blocks,

@@ -148,6 +148,14 @@ inline uint64_t merkle_pieces_work(uint32_t n, uint32_t log2_width) {  // bytes 
 hipError_t launch_merkle_pieces(const uint8_t* base, const uint64_t* offsets, const uint32_t* lens,
                                 const uint8_t* log2w, uint32_t n, uint32_t log2_width, uint8_t* work, uint8_t* roots,
                                 const uint8_t* expected, uint8_t* matched, hipStream_t stream);
+// The block check (vx_merkle_device_block_check): the ragged batch's leaves
+// against row g of expected_leaves, one bit per block into bad (uint64 words,
+// max(1, 2^log2_width / 64) per piece, every word written) and / or the leaf
+// rows into leaves_out.  expected_leaves and bad are both given or both NULL;
+// n >= 1.
+hipError_t launch_merkle_block_check(const uint8_t* base, const uint64_t* offsets, const uint32_t* lens, uint32_t n,
+                                     uint32_t log2_width, const uint8_t* expected_leaves, uint64_t* bad,
+                                     uint8_t* leaves_out, hipStream_t stream);
 // The two halves on their own (the re-verify from disk): the block kernel
 // hashes stage block b (lens[b] <= 16384 bytes at stage + b*16384) into leaf
 // row rows[b] (0xFFFFFFFF: none; lens[b] == 0: the zero hash, nothing read);

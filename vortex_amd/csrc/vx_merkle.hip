@@ -1,7 +1,9 @@
 // vx_merkle.hip — the BitTorrent v2 merkle entries of vx_hash.h (kernels in
 // sha256_kernels.hip): vx_merkle_device_*, _verify_batch, _verify_files,
-// _layers_plan, _verify_layers, _verify_proofs; the layer trees (_tree_plan,
-// _device_trees, _build_trees, _tree_proof, _tree_layout) and _hash_files.
+// _layers_plan, _verify_layers, _verify_proofs; the block checks
+// (_bitmap_words, _device_block_check, _check_blocks); the layer trees
+// (_tree_plan, _device_trees, _build_trees, _tree_proof, _tree_layout) and
+// _hash_files.
 #include "vx_engine_internal.hpp"
 #include "vx_merkle_layers.hpp"
 #include "vx_merkle_tree.hpp"
@@ -807,6 +809,132 @@ int vx_merkle_verify_proofs(vx_ctx* c, const uint8_t* hashes, uint64_t n_rows, c
     if (tops_out) VX_HIP(hipMemcpyAsync(tops_out, b.d + o_tops, (size_t)n * 32, hipMemcpyDeviceToHost, b.stream));
     VX_HIP(hipMemcpyAsync(matched_out, b.d + o_match, n, hipMemcpyDeviceToHost, b.stream));
     VX_HIP(hipStreamSynchronize(b.stream));
+    return 0;
+}
+
+// ---- block checks ("Block checks") ----
+
+uint64_t vx_merkle_bitmap_words(uint32_t n, uint32_t log2_width) {
+    if (log2_width > VX_MERKLE_MAX_LOG2_WIDTH) return 0;
+    return (uint64_t)n * std::max<uint64_t>(1, (1ull << log2_width) / 64);
+}
+
+int vx_merkle_device_block_check(const void* d_base, const uint64_t* d_offsets, const uint32_t* d_lens, uint32_t n,
+                                 uint32_t log2_width, const void* d_expected_leaves, uint64_t* d_bad,
+                                 void* d_leaves_out, void* stream) {
+    if (n == 0) return 0;
+    const char* who = "vx_merkle_device_block_check";
+    // (d_base stands in for the leaf array merkle_args also checks when the call keeps none)
+    int rc = merkle_args(who, d_base, d_leaves_out ? d_leaves_out : d_base, n, log2_width);
+    if (rc) return rc;
+    if (!d_offsets || !d_lens) return fail(VX_EINVAL, std::string(who) + ": NULL d_offsets or d_lens");
+    if (!d_expected_leaves != !d_bad)
+        return fail(VX_EINVAL, std::string(who) + ": d_expected_leaves and d_bad are given together or not at all");
+    if (!d_expected_leaves && !d_leaves_out)
+        return fail(VX_EINVAL, std::string(who) + ": neither a bitmap nor d_leaves_out asked for");
+    if ((reinterpret_cast<uintptr_t>(d_expected_leaves) & 15) || (reinterpret_cast<uintptr_t>(d_bad) & 7))
+        return fail(VX_EINVAL, std::string(who) + ": d_expected_leaves must be 16-byte and d_bad 8-byte aligned");
+    hipError_t e = vx::launch_merkle_block_check(static_cast<const uint8_t*>(d_base), d_offsets, d_lens, n, log2_width,
+                                                 static_cast<const uint8_t*>(d_expected_leaves), d_bad,
+                                                 static_cast<uint8_t*>(d_leaves_out), static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "merkle block check kernel launch");
+    return 0;
+}
+
+int vx_merkle_check_blocks(vx_ctx* c, const uint8_t* const* ptrs, const uint32_t* lens, size_t n,
+                           uint32_t piece_length, const uint8_t* expected_leaves, uint64_t* bad_out,
+                           uint32_t* bad_counts_out, uint8_t* leaves_out) {
+    const char* who = "vx_merkle_check_blocks";
+    if (!c) return fail(VX_EINVAL, std::string(who) + ": NULL context");
+    if (n && (!ptrs || !lens)) return fail(VX_EINVAL, std::string(who) + ": NULL ptrs/lens");
+    if (n && !expected_leaves != !bad_out)
+        return fail(VX_EINVAL, std::string(who) + ": bad_out is required iff expected_leaves is given");
+    if (n && !expected_leaves && bad_counts_out)
+        return fail(VX_EINVAL, std::string(who) + ": bad_counts_out needs expected_leaves");
+    if (n && !expected_leaves && !leaves_out)
+        return fail(VX_EINVAL, std::string(who) + ": neither expected_leaves nor leaves_out given");
+    if (piece_length < VX_MERKLE_BLOCK || (piece_length & (piece_length - 1)))
+        return fail(VX_EINVAL, std::string(who) + ": piece_length must be a power of two >= 16384");
+    if (piece_length > c->cfg.max_piece_len) return fail(VX_ERANGE, std::string(who) + ": piece_length > max_piece_len");
+    uint32_t log2_width = 0;
+    while (((uint32_t)VX_MERKLE_BLOCK << log2_width) < piece_length) ++log2_width;
+    for (size_t i = 0; i < n; ++i) {  // argument errors before anything is allocated or copied
+        if (lens[i] > piece_length) return fail(VX_EINVAL, std::string(who) + ": piece longer than piece_length");
+        if (lens[i] && !ptrs[i]) return fail(VX_EINVAL, std::string(who) + ": NULL piece pointer");
+    }
+    if (n == 0) return 0;
+    if (c->sticky) return c->sticky;
+    // Rounds: as many pieces as slot_bytes of 16-byte aligned piece bytes and
+    // slot_bytes / 16 KiB leaf rows hold (one piece at least: piece_length <=
+    // max_piece_len <= slot_bytes).  Planned first, so the one device block is
+    // sized for the largest of them.
+    const uint64_t W = 1ull << log2_width, wpp = std::max<uint64_t>(1, W / 64);
+    const uint64_t cap_bytes = c->cfg.slot_bytes;
+    const uint64_t cap_pieces = std::max<uint64_t>(1, (cap_bytes / VX_MERKLE_BLOCK) >> log2_width);
+    auto round_at = [&](size_t first, uint64_t* bytes_out) -> uint32_t {
+        uint32_t m = 0;
+        uint64_t bytes = 0;
+        while (first + m < n && m < cap_pieces && bytes + align_up(lens[first + m], 16) <= cap_bytes)
+            bytes += align_up(lens[first + m++], 16);
+        *bytes_out = bytes;
+        return m;
+    };
+    uint64_t max_m = 0, max_bytes = 0;
+    for (size_t first = 0; first < n;) {
+        uint64_t bytes;
+        const uint32_t m = round_at(first, &bytes);
+        if (m == 0) return fail(VX_ERANGE, std::string(who) + ": a piece does not fit slot_bytes");
+        max_m = std::max<uint64_t>(max_m, m);
+        max_bytes = std::max(max_bytes, bytes);
+        first += m;
+    }
+    // arena | expected rows | leaf rows | offsets | bitmap | lens: each part as aligned as it must be
+    const uint64_t o_exp = align_up(std::max<uint64_t>(max_bytes, 16), 16);
+    const uint64_t o_leaves = o_exp + (expected_leaves ? max_m * W * 32 : 0);
+    const uint64_t o_offs = o_leaves + (leaves_out ? max_m * W * 32 : 0);
+    const uint64_t o_bad = o_offs + max_m * 8;
+    const uint64_t o_lens = o_bad + (expected_leaves ? max_m * wpp * 8 : 0);
+    CallBufs b;
+    int rc = b.make(c, o_lens + max_m * 4, who);
+    if (rc) return rc;
+    std::vector<uint64_t> offs(max_m);
+    for (size_t first = 0; first < n;) {
+        uint64_t bytes;
+        const uint32_t m = round_at(first, &bytes);
+        uint64_t at = 0;
+        for (uint32_t j = 0; j < m; ++j) {
+            const size_t i = first + j;
+            offs[j] = at;
+            if (lens[i]) VX_HIP(hipMemcpyAsync(b.d + at, ptrs[i], lens[i], hipMemcpyHostToDevice, b.stream));
+            at += align_up(lens[i], 16);
+        }
+        const uint64_t rows = (uint64_t)m * W;
+        VX_HIP(hipMemcpyAsync(b.d + o_offs, offs.data(), (size_t)m * 8, hipMemcpyHostToDevice, b.stream));
+        VX_HIP(hipMemcpyAsync(b.d + o_lens, lens + first, (size_t)m * 4, hipMemcpyHostToDevice, b.stream));
+        if (expected_leaves)
+            VX_HIP(hipMemcpyAsync(b.d + o_exp, expected_leaves + first * W * 32, rows * 32, hipMemcpyHostToDevice,
+                                  b.stream));
+        rc = vx_merkle_device_block_check(b.d, reinterpret_cast<const uint64_t*>(b.d + o_offs),
+                                          reinterpret_cast<const uint32_t*>(b.d + o_lens), m, log2_width,
+                                          expected_leaves ? b.d + o_exp : nullptr,
+                                          expected_leaves ? reinterpret_cast<uint64_t*>(b.d + o_bad) : nullptr,
+                                          leaves_out ? b.d + o_leaves : nullptr, b.stream);
+        if (rc) return rc;
+        if (expected_leaves)
+            VX_HIP(hipMemcpyAsync(bad_out + first * wpp, b.d + o_bad, (size_t)m * wpp * 8, hipMemcpyDeviceToHost,
+                                  b.stream));
+        if (leaves_out)
+            VX_HIP(hipMemcpyAsync(leaves_out + first * W * 32, b.d + o_leaves, rows * 32, hipMemcpyDeviceToHost,
+                                  b.stream));
+        VX_HIP(hipStreamSynchronize(b.stream));  // offs and the arena are the next round's
+        first += m;
+    }
+    if (bad_counts_out)
+        for (size_t i = 0; i < n; ++i) {
+            uint32_t count = 0;
+            for (uint64_t k = 0; k < wpp; ++k) count += (uint32_t)__builtin_popcountll(bad_out[i * wpp + k]);
+            bad_counts_out[i] = count;
+        }
     return 0;
 }
 

@@ -344,6 +344,75 @@ def merkle_pieces(data: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor,
     return roots, matched
 
 
+def merkle_block_check(data: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor, log2_width: int,
+                       expected_leaves: Optional[torch.Tensor] = None, leaves: Optional[torch.Tensor] = None,
+                       stream: Optional[torch.cuda.Stream] = None, bad: Optional[torch.Tensor] = None,
+                       want_leaves: Optional[bool] = None, validate: bool = True):
+    """Check the batch of :func:`merkle_ragged` (every piece a tree of
+    2^log2_width slots) block by block (vx_merkle_device_block_check):
+    expected_leaves holds the (n << log2_width) * 32 bytes a merkle_ragged call
+    on good data writes to `leaves`.  One launch.
+
+    Returns (bad, leaves).  bad: int64 [merkle.bitmap_words(n, log2_width)], the
+    bitmap's uint64 words bit for bit (torch has little arithmetic for uint64;
+    ``bad.cpu().numpy().view("uint64")``): block b of piece i is bit b & 63 of
+    word i * max(1, 2^log2_width / 64) + (b >> 6).  Every word is written; a
+    slot at or past a piece's end is never set.  None without expected_leaves.
+    leaves: the leaf rows [n << log2_width, 32], kept when `leaves` is given or
+    want_leaves is true (the default without expected_leaves), else None.
+    Layout checks (validate) as for merkle_ragged."""
+    _req(data, "data")
+    _req(offsets, "offsets", torch.int64)
+    _req(lens, "lens", torch.int32)
+    n = offsets.numel()
+    if lens.numel() != n:
+        raise ValueError("offsets and lens differ in length")
+    if not 0 <= log2_width <= 17:
+        raise ValueError("log2_width must be 0..17")
+    rows = n << log2_width
+    if rows >> 32:
+        raise ValueError("n << log2_width must fit 32 bits")
+    dev = data.device
+    for name, t in (("offsets", offsets), ("lens", lens), ("expected_leaves", expected_leaves), ("leaves", leaves),
+                    ("bad", bad)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, data on {dev}")
+    if want_leaves is None:
+        want_leaves = leaves is not None or expected_leaves is None
+    if expected_leaves is None and not want_leaves:
+        raise ValueError("merkle_block_check: neither expected_leaves nor leaves asked for")
+    words = n * max(1, (1 << log2_width) // 64)
+    if expected_leaves is not None:
+        _req(expected_leaves, "expected_leaves")
+        if expected_leaves.numel() < 32 * rows:
+            raise ValueError("expected_leaves must hold (n << log2_width)*32 bytes")
+        if bad is None:
+            bad = torch.empty((words,), dtype=torch.int64, device=dev)
+        else:
+            _req(bad, "bad", torch.int64)
+            if bad.numel() < words:
+                raise ValueError("bad must hold merkle.bitmap_words(n, log2_width) words")
+    elif bad is not None:
+        raise ValueError("bad needs expected_leaves")
+    if not want_leaves:
+        leaves = None
+    elif leaves is None:
+        leaves = torch.empty((rows, 32), dtype=torch.uint8, device=dev)
+    else:
+        _req(leaves, "leaves")
+        if leaves.numel() < 32 * rows:
+            raise ValueError("leaves must hold (n << log2_width)*32 bytes")
+    if validate:
+        _check_merkle_layout(data, offsets, lens, None, log2_width, "merkle_block_check")
+    rc = lib().vx_merkle_device_block_check(data.data_ptr(), offsets.data_ptr(), lens.data_ptr(), n, log2_width,
+                                            expected_leaves.data_ptr() if expected_leaves is not None else None,
+                                            bad.data_ptr() if bad is not None else None,
+                                            leaves.data_ptr() if leaves is not None else None,
+                                            _stream_ptr(stream, dev))
+    check(rc, "vx_merkle_device_block_check")
+    return bad, leaves
+
+
 def hybrid_work_bytes(n: int, log2_width: int) -> int:
     """Bytes of the work tensor of :func:`hybrid_pieces` (vx_hash.h,
     vx_hybrid_device_pieces): the merkle piece kernel's work rounded up to 16,

@@ -575,6 +575,49 @@ class HashPool:
                                                None), "vx_merkle_verify_proofs", self.lib)
         return [bool(b) for b in out.raw[:n]]
 
+    def check_blocks(self, pieces: Sequence, piece_length: int, expected_leaves: Optional[Sequence[bytes]] = None,
+                     want_leaves: bool = False) -> tuple[Optional[list[list[int]]], Optional[list[bytes]]]:
+        """Which 16 KiB blocks of v2 pieces are wrong (vx_merkle_check_blocks):
+        expected_leaves[i] is piece i's leaf layer, piece_length / 16 KiB rows
+        of 32 bytes, as a peer sent it for a `hashes` request at base layer 0
+        and verify_hash_proofs accepted it against the piece's trusted row.
+        Every piece is a tree of piece_length / 16 KiB slots.  Works while
+        async pieces are pending and leaves stats() alone.
+
+        Returns (bad, leaves): bad[i] the indices of piece i's bad blocks, in
+        order (None without expected_leaves; a slot at or past the piece's end
+        is never bad); leaves[i] the piece's own leaf layer
+        (merkle.leaf_rows), what a seeder answers such a request from (None
+        unless want_leaves)."""
+        n = len(pieces)
+        lw = merkle.log2_width(piece_length)
+        rows = 1 << lw
+        if expected_leaves is None and not want_leaves:
+            raise ValueError("check_blocks: neither expected_leaves nor want_leaves")
+        if expected_leaves is not None and (len(expected_leaves) != n or
+                                            any(len(e) != 32 * rows for e in expected_leaves)):
+            raise ValueError("expected_leaves must hold piece_length / 16 KiB rows of 32 bytes per piece")
+        ptrs, lens, keep = _ptr_arrays(pieces)
+        wpp = max(1, rows // 64)
+        exp = bad = counts = out = None
+        if expected_leaves is not None:
+            exp = ctypes.create_string_buffer(b"".join(bytes(e) for e in expected_leaves), 32 * rows * max(n, 1))
+            bad = (ctypes.c_uint64 * max(n * wpp, 1))()
+            counts = (ctypes.c_uint32 * max(n, 1))()
+        if want_leaves:
+            out = ctypes.create_string_buffer(32 * rows * max(n, 1))
+        check(self.lib.vx_merkle_check_blocks(self._h, ptrs, lens, n, piece_length, exp, bad, counts, out),
+              "vx_merkle_check_blocks", self.lib)
+        lists = None
+        if bad is not None:
+            lists = [[64 * k + b for k in range(wpp) for b in range(64) if bad[i * wpp + k] >> b & 1]
+                     if counts[i] else [] for i in range(n)]
+        leaves = None
+        if out is not None:
+            view = memoryview(out)
+            leaves = [bytes(view[32 * rows * i:32 * rows * (i + 1)]) for i in range(n)]
+        return lists, leaves
+
     def verify_merkle_files(self, paths: Sequence[str], file_lengths: Sequence[int], piece_length: int,
                             expected: bytes, io_threads: int = 0, first: int = 0,
                             count: int | None = None) -> tuple[list[bool], int]:

@@ -216,3 +216,63 @@ def make_proof(layer, height: int, pos: int, span: int, uncles: int) -> bytes:
     base = span.bit_length() - 1
     out += [tree.node(base + k, (pos >> k) ^ 1) for k in range(uncles)]
     return b"".join(out)
+
+
+def bitmap_words(n: int, log2_width: int) -> int:
+    """uint64 words of the bad-block bitmap of n pieces of 2^log2_width leaf
+    slots (vx_merkle_bitmap_words): max(1, 2^log2_width / 64) per piece; block b
+    of piece i is bit b & 63 of word i * wpp + (b >> 6).  0 for a width above
+    MAX_LOG2_WIDTH."""
+    if n < 0 or log2_width < 0:
+        raise ValueError("n and log2_width must be >= 0")
+    if log2_width > MAX_LOG2_WIDTH:
+        return 0
+    return n * max(1, (1 << log2_width) // 64)
+
+
+def leaf_rows(data, log2w: int) -> bytes:
+    """The leaf layer of one piece as a tree of 2^log2w slots, with hashlib:
+    SHA-256 of each 16 KiB block (the last at its real length), zero rows for
+    the slots at or past the piece's end; (32 << log2w) bytes.  What
+    ``device.merkle_block_check`` and ``HashPool.check_blocks`` return."""
+    data = bytes(data)
+    if not 0 <= log2w <= MAX_LOG2_WIDTH:
+        raise ValueError("log2w must be 0..17")
+    if len(data) > BLOCK << log2w:
+        raise ValueError("the piece is longer than its tree (16384 << log2w bytes)")
+    return b"".join(hashlib.sha256(data[o:o + BLOCK]).digest() if o < len(data) else bytes(32)
+                    for o in range(0, BLOCK << log2w, BLOCK))
+
+
+def bad_blocks(data, expected_leaves) -> list[int]:
+    """The blocks of one piece whose SHA-256 differs from their row of
+    expected_leaves (the piece's 2^log2w leaf rows): the model of the
+    bad-block bitmap.  A slot at or past the piece's end is never bad,
+    whatever its expected row holds."""
+    data = bytes(data)
+    rows = _rows(expected_leaves)
+    if len(data) > BLOCK * len(rows):
+        raise ValueError("the piece is longer than its expected leaf rows")
+    return [b for b in range((len(data) + BLOCK - 1) // BLOCK)
+            if hashlib.sha256(data[b * BLOCK:(b + 1) * BLOCK]).digest() != rows[b]]
+
+
+def block_proof(leaves, file_tree: bytes, m: int, height: int, piece: int, pos: int, span: int) -> bytes:
+    """The `hashes` message for a base-layer-0 request of `span` leaf hashes (a
+    power of two) at span number `pos` inside piece `piece` of a file: `leaves`
+    is that piece's leaf layer (2^height rows, :func:`leaf_rows`), file_tree the
+    tree of the file's m-row piece layer (:func:`build_tree` at `height`).  Rows,
+    in order: the span's, the log2(2^height / span) uncles inside the piece,
+    then the ceil(log2 m) uncles above it out of file_tree.  Equal to
+    make_proof over the file's whole leaf layer at span number
+    piece * (2^height / span) + pos."""
+    rows = _rows(leaves)
+    if len(rows) != 1 << height:
+        raise ValueError("leaves must hold the piece's 2^height rows")
+    if span < 1 or span & (span - 1) or span > len(rows):
+        raise ValueError("span must be a power of two of at most 2^height")
+    if not 0 <= piece < m or not 0 <= pos < len(rows) // span:
+        raise ValueError("piece or pos outside the file")
+    inside = make_proof(rows, 0, pos, span, height - (span.bit_length() - 1))
+    above = proof_from_tree(file_tree, m, height, 0, piece, 1, (m - 1).bit_length())
+    return inside + above[32:]
