@@ -3,7 +3,9 @@
   * leaf lengths 128 g + r around the leaf kernels' two-group ring: the tail
     lengths of test_gpu_merkle*.py all sit at g <= 1 or g = 127;
   * per-piece widths (log2w) under a batch wider than one node tile
-    (log2_width = 10): so far log2w was only combined with widths <= 9;
+    (log2_width = 10, the smallest such width; widths 11 to 17, where the
+    wide kernels have more than two tiles per piece, are in
+    test_gpu_merkle_wide.py);
   * verdicts against an expected root that is one bit off, a different byte
     for every piece: so far a mismatch was a flipped data byte or a zero row;
   * pieces at offsets at or above 4 GiB.

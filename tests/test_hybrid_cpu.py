@@ -352,6 +352,25 @@ def test_planner_layouts(dump_exe, name, pl, flens):
         replay(dump_exe, flens, pl, 8 * BLOCK, chunk=2 * BLOCK, first=1, count=n - 2)
 
 
+M32 = 32 << 20
+LARGE = [  # (piece_length, file_lengths, stage bytes, first, count): trees of 2^11 and 2^12 leaf slots
+    (M32, [M32 + 1, 5, 2 * M32 + BLOCK + 7, 3 * BLOCK], 64 << 20, 0, -1),
+    (M32, [M32 + 1, 5, 2 * M32 + BLOCK + 7, 3 * BLOCK], 64 << 20, 1, 3),
+    (M32, [M32 + 12345, 100, M32 - 1], 8 << 20, 0, -1),   # a stage of a quarter piece
+    (64 << 20, [70, (64 << 20) + 65], 64 << 20, 0, -1),   # a stage of exactly one piece
+]
+
+
+@pytest.mark.parametrize("pl,flens,stage,first,count", LARGE, ids=["32MiB", "32MiB-range", "32MiB-stage8", "64MiB"])
+def test_planner_large_piece_lengths(dump_exe, pl, flens, stage, first, count):
+    """Pieces above 16 MiB: every piece takes many chunk rounds, a padded piece
+    of 1 or 5 bytes has a pad of almost the whole piece, and a window holds
+    2,048 or 4,096 rows per piece."""
+    rounds, s = replay(dump_exe, flens, pl, stage, first=first, count=count)
+    assert max(r["K"] for r in rounds) == (pl // BLOCK).bit_length() - 1
+    assert any(not r["new"] for r in rounds), "pieces take several chunk rounds"
+
+
 def test_planner_random_torrents(dump_exe):
     rng = random.Random(20)
     for t in range(20):

@@ -166,3 +166,34 @@ def test_file_pieces_against_python_tree(piece_length):
         merkle.file_pieces(1, piece_length + 1)
     with pytest.raises(ValueError):
         merkle.log2_width(8192)
+
+
+def test_device_lens_are_int32_and_a_2_gib_piece_is_refused():
+    """device.py's layout check on host tensors (it runs wherever its tensors
+    live): a full piece of a 2^17-slot tree is 2^31 bytes, which the C ABI's
+    uint32 holds and an int32 tensor does not; its bits there are a negative
+    length, refused by name.  2^31 - 1 bytes, the longest piece lens can hold,
+    pass at width 17 and are too long for width 16."""
+    import torch
+
+    from vortex_amd import device as vdev
+
+    class Sized:  # stands for a 2 GiB data tensor: the check reads its numel() only
+        @staticmethod
+        def numel():
+            return 1 << 31
+
+    offs = torch.tensor([0], dtype=torch.int64)
+    with pytest.raises((RuntimeError, OverflowError)):
+        torch.tensor([1 << 31], dtype=torch.int32)
+    wrapped = torch.tensor([-1 << 31], dtype=torch.int32)  # the bits of uint32 2^31
+    for who in ("merkle_ragged", "merkle_pieces", "merkle_block_check", "hybrid_pieces"):
+        with pytest.raises(ValueError, match=who + ": negative offset or length .*2\\^31 bytes"):
+            vdev._check_merkle_layout(Sized, offs, wrapped, None, 17, who)
+    longest = torch.tensor([(1 << 31) - 1], dtype=torch.int32)
+    vdev._check_merkle_layout(Sized, offs, longest, None, 17)
+    vdev._check_merkle_layout(Sized, offs, longest, torch.tensor([17], dtype=torch.uint8), 17)
+    with pytest.raises(ValueError, match="longer than its tree"):
+        vdev._check_merkle_layout(Sized, offs, longest, None, 16)
+    with pytest.raises(ValueError, match="longer than its tree"):
+        vdev._check_merkle_layout(Sized, offs, longest, torch.tensor([16], dtype=torch.uint8), 17)

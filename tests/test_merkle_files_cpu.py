@@ -308,6 +308,29 @@ def test_packer_small_window_and_small_tables(dump):
     _check(dump, [16385] * 40, 1 << 20, 16, window=1024, entries=16 + 64)
 
 
+LARGE = [  # (piece_length, file_lengths, blocks_per_round): trees of 2^11, 2^13 and 2^17 (the widest) leaf slots
+    (32 << 20, lambda pl: [pl + 1, 5, 2 * pl + BLOCK + 7], 256),
+    (32 << 20, lambda pl: [pl + 1], 16),
+    (1 << 27, lambda pl: [2 * pl + 77, 9], 1024),
+    (1 << 31, lambda pl: [pl + 1], 4096),
+    (1 << 31, lambda pl: [3 * BLOCK + 5, pl + BLOCK, 1], 16384),
+]
+
+
+@pytest.mark.parametrize("pl,flens,bpr", LARGE, ids=[f"{pl >> 20}MiB-{k}" for k, (pl, _, _) in enumerate(LARGE)])
+def test_packer_large_piece_lengths(dump, pl, flens, bpr):
+    """Pieces of 32 MiB, 128 MiB and 2 GiB (VX_MERKLE_MAX_LOG2_WIDTH): a piece
+    takes many rounds, and a one-byte piece behind a full one leaves up to
+    2^17 - 1 absent slots."""
+    from vortex_amd import merkle
+
+    flens = flens(pl)
+    rounds, s = _check(dump, flens, pl, bpr)
+    assert s["blocks"] == sum(-(-n // BLOCK) for n in flens)
+    assert s["entries"] == sum(1 << w for w in merkle.torrent_pieces(flens, pl)[1])
+    assert max(n[2] for r in rounds for n in r["nodes"]) == merkle.log2_width(pl)
+
+
 def test_packer_100k_files(dump):
     """10^5 files: the packer walks pieces, not files per piece; its time is
     bounded as the v1 segment walk's is (tests/test_native_cpu.py), here under

@@ -237,7 +237,12 @@ def _check_merkle_layout(data: torch.Tensor, offsets: torch.Tensor, lens: torch.
     """What :func:`_check_ragged_layout` checks for sha1_ragged, for a merkle
     batch: offsets 16-byte aligned and >= 0, lengths >= 0, every piece inside
     `data`, every log2w <= log2_width and every piece inside its own tree
-    (16384 << log2w bytes).  One device reduction and one copy back (a sync)."""
+    (16384 << log2w bytes).  One device reduction and one copy back (a sync).
+
+    `lens` is int32 here, so a piece is at most 2^31 - 1 bytes.  The C entries
+    take uint32 lengths, and exactly one length above that is valid there: 2^31,
+    the full 2 GiB piece of a tree of 2^17 slots.  This module refuses it: its
+    bits in an int32 tensor are a negative length, and the ValueError says so."""
     if offsets.numel() == 0:
         return
     ends = offsets + lens.to(torch.int64)
@@ -252,7 +257,8 @@ def _check_merkle_layout(data: torch.Tensor, offsets: torch.Tensor, lens: torch.
     if stats[0]:
         raise ValueError(f"{who}: every offset must be a multiple of 16 (the kernels load 16 bytes per lane)")
     if stats[1]:
-        raise ValueError(f"{who}: negative offset or length")
+        raise ValueError(f"{who}: negative offset or length (lens is int32: a piece of 2^31 bytes, the full tree of "
+                         "2^17 slots, has no length here and is refused)")
     if stats[2] > data.numel():
         raise ValueError(f"{who}: a piece ends at byte {stats[2]}, past the data tensor "
                          f"({data.numel()} bytes)")
@@ -272,6 +278,10 @@ def merkle_ragged(data: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor,
     values); lens: int32; log2w: optional uint8, piece i's own tree width
     (<= log2_width; merkle.file_pieces).  Piece i's leaf rows start at row
     i << log2_width whatever its log2w.  validate: as for :func:`sha1_ragged`.
+    log2_width goes up to 17; lens being int32, a piece is at most 2^31 - 1
+    bytes, and the full 2^31-byte piece of width 17 is refused
+    (:func:`_check_merkle_layout`; the same holds for merkle_pieces,
+    merkle_block_check and hybrid_pieces).
 
     Returns (roots [n,32], leaves [n << log2_width, 32], matched [n] or None)."""
     _req(data, "data")
