@@ -65,6 +65,18 @@ int vx_tuning_zero_tail_kernel(const void* d_base, const uint64_t* d_tail_offs, 
 int vx_tuning_chunk_kernel(const void* d_base, const uint64_t* d_offsets, const uint32_t* d_lens, uint32_t n,
                            const uint32_t* d_pids, const uint64_t* d_poffs, const uint64_t* d_tlens,
                            uint32_t* d_states, void* d_digests, void* stream);
+/* The kernel that ends a hybrid download slot on its own (DESIGN.md §3.8,
+ * §6.9; tests/test_gpu_hybrid_tail_sweep.py): lane j with d_pads[j] != 0
+ * finishes its piece as the zero-tail kernel does (every padded piece is
+ * padded_total bytes, a multiple of 64) into d_digests row j; every lane then
+ * compares d_digests row j and d_roots row j (n x 32 B) with row
+ * d_exp_index[j] (NULL: j) of d_exp_sha1 / d_exp_roots where d_flags[j] bit 0 /
+ * bit 1 is set, and writes the verdict bits to d_matched[j].  Enqueue-only. */
+int vx_tuning_hybrid_finish_kernel(const void* d_base, const uint64_t* d_tail_offs, const uint32_t* d_lens,
+                                   const uint32_t* d_pads, uint32_t n, uint64_t padded_total,
+                                   const uint32_t* d_states, void* d_digests, const void* d_roots,
+                                   const void* d_exp_sha1, const void* d_exp_roots, const uint32_t* d_exp_index,
+                                   const uint8_t* d_flags, void* d_matched, void* stream);
 /* Fault injection for tests: after k more successful piece submits (async or
  * inside a host batch), the next one fails with VX_ENOMEM without latching
  * the context, as a failed pinned-stage allocation does.  k < 0 turns it off. */

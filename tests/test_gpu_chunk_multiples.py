@@ -11,6 +11,7 @@ tests/test_sha1_sweep_cpu.py checks with vx_tuning_chunk_schedule that these
 cases really hold such rounds.  Written as test_verify_files_chunk_schedule,
 test_strided_batch_chunked and test_gather_batch_chunked (test_gpu_parity.py)
 are; verdicts against the oracle, digests against hashlib.
+(tests/test_gpu_sha1_chunk_sweep.py runs the chunk kernel alone at every edge of both phases, states compared.)
 """
 import hashlib
 import mmap

@@ -7,6 +7,7 @@ Every expectation is hashlib's: SHA-1 over the data followed by its pad zeros
 Everything is bit-exact.  Data is np.random.default_rng(seed) bytes; the device
 buffers hold 0xFF wherever no piece has a byte, so a kernel that read past a
 piece's data would hash something hashlib did not.
+(tests/test_gpu_hybrid_tail_sweep.py runs the tail and finish kernels alone over every tail length.)
 """
 import ctypes
 import hashlib

@@ -119,6 +119,80 @@ def test_h_and_m_reach_all_nine_phase_combinations():
     assert [64 * 6 + 0] * 63 + [64 * 6 + 63] in [sorted(w) for w in sw.recipe_m()]
 
 
+# ---------------------------------------------------------------------------
+# The resumable chunk kernel: lanes are (length, final)
+# ---------------------------------------------------------------------------
+def _chunk_reachable():
+    """Every class a wave of two kinds of lane can take, nfull 0..63."""
+    kinds = sw.CHUNK_KINDS
+    return {sw.class_chunk([a, b]) for i, a in enumerate(kinds) for b in kinds[i:]}
+
+
+def _chunk_classes(recipes):
+    waves = [w for r in recipes for w in sw.waves_of(sw.chunk_batch(r))]
+    return {sw.class_chunk(w) for w in waves if len(set(w)) <= 2}
+
+
+def test_chunk_classifier_reads_nfull_pad_and_final_only():
+    """What lets the brute force use four tails per block count: as
+    test_wave_classifiers_read_nfull_and_pad_only, for the final lanes."""
+    others = [(64 * 7 + 56, True), (64 * 9, False)]
+    for L in range(4096):
+        rep = (L & ~63) + (56 if (L & 63) > 55 else 0)
+        for o in others:
+            assert sw.class_chunk([(L, True), o]) == sw.class_chunk([(rep, True), o])
+    with pytest.raises(AssertionError):
+        sw.class_chunk([(100, False)])  # a lane that does not end its piece is whole blocks
+    with pytest.raises(AssertionError):
+        sw.class_chunk([(0, False)])
+
+
+def test_chunk_recipes_cover_the_chunk_kernel():
+    """Every class that a wave of two kinds of lane can take is taken by a wave
+    the GPU sweep launches (tests/test_gpu_sha1_chunk_sweep.py runs every
+    recipe's batch)."""
+    reachable = _chunk_reachable()
+    _missing(reachable, _chunk_classes(sw.CHUNK_RECIPES), "class_chunk")
+    for r in sw.CHUNK_RECIPES:
+        assert len(sw.chunk_batch(r)) % sw.WAVE == 1  # a last wave of one live lane
+    # the holes the sweep is there for: a wave without phase 2 after zero, one and more
+    # trips of phase 1 cannot exist (b1 == nb_wave > 0 needs a trip), after one and more it does;
+    # every nfull % kBlockRing of whole-block lanes; a final lane among whole-block lanes
+    got = _chunk_classes(sw.CHUNK_RECIPES)
+    assert {c[0] for c in got if c[2]} == {1, 2} and all(c[1] == 0 and c[4] and not c[3] for c in got if c[2])
+    whole = {x[0] >> 6 for w in sw.chunk_waves("whole") for x in w}
+    assert {f % sw.kBlockRing for f in whole} == set(range(sw.kBlockRing))
+    assert any(c[4] and c[5] and c[6] for c in got)
+
+
+def test_the_chunk_coverage_check_notices_a_dropped_recipe():
+    """Without the mixed recipes (and the cover, which is built from what the
+    recipes leave out) the check fails and names the missing classes; and every
+    wave of the cover is needed."""
+    reachable = _chunk_reachable()
+    with pytest.raises(AssertionError, match=r"class_chunk: \d+ of \d+ reachable classes are not covered: \[\("):
+        _missing(reachable, _chunk_classes(("final", "whole")), "class_chunk")
+    with pytest.raises(AssertionError, match=r"class_chunk: \d+ of \d+ reachable classes are not covered: \[\("):
+        _missing(reachable, _chunk_classes(sw.CHUNK_RECIPES[:-1]), "class_chunk")
+    seen = {sw.class_chunk(w) for r in sw.CHUNK_RECIPES[:-1] for w in sw.chunk_waves(r)}
+    for w in sw.chunk_cover():
+        assert sw.class_chunk(w) not in seen, w
+        seen.add(sw.class_chunk(w))
+
+
+def test_chain_plan_cuts_every_grid_piece_at_the_ring_edges():
+    plan = sw.chain_plan()
+    assert [L for L, _ in plan] == [L for L in sw.GRID if L > 64]
+    used = set()
+    for L, chunks in plan:
+        assert 2 <= len(chunks) <= 4 and sum(chunks) == L and chunks[-1] > 0
+        assert all(c % 64 == 0 and c >> 6 in sw.CHAIN_CUTS for c in chunks[:-1])
+        used.update(c >> 6 for c in chunks[:-1])
+    assert used == set(sw.CHAIN_CUTS)
+    assert any(chunks[-1] == 64 for _, chunks in plan) and any(chunks[-1] < 56 for _, chunks in plan)
+    assert {len(chunks) for _, chunks in plan} == {2, 3, 4}
+
+
 def _schedule(L, C, head, tail):
     from vortex_amd import _lib
 

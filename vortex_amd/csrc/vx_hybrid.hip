@@ -1,7 +1,7 @@
 // vx_hybrid.hip — the hybrid (BEP 52 "upgrade path", v1 + v2) entries of
 // vx_hash.h: vx_hybrid_device_pieces and vx_hybrid_verify_files / _range
 // (kernels in sha1_kernels.hip, sha1_tail_kernels.hip and sha256_kernels.hip;
-// the rounds in vx_hybrid_rounds.hpp), and the two tuning kernel entries.  The
+// the rounds in vx_hybrid_rounds.hpp), and the three tuning kernel entries.  The
 // hybrid download path (vx_hybrid_submit) is in vx_slots.hip.
 #include "vx_chunk_pipe.hpp"
 #include "vx_hybrid_rounds.hpp"
@@ -393,6 +393,25 @@ int vx_tuning_chunk_kernel(const void* d_base, const uint64_t* d_offsets, const 
                                     d_states, static_cast<uint8_t*>(d_digests), nullptr, nullptr,
                                     static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : hip_fail(e, "vx_tuning_chunk_kernel");
+}
+
+int vx_tuning_hybrid_finish_kernel(const void* d_base, const uint64_t* d_tail_offs, const uint32_t* d_lens,
+                                   const uint32_t* d_pads, uint32_t n, uint64_t padded_total,
+                                   const uint32_t* d_states, void* d_digests, const void* d_roots,
+                                   const void* d_exp_sha1, const void* d_exp_roots, const uint32_t* d_exp_index,
+                                   const uint8_t* d_flags, void* d_matched, void* stream) {
+    if (n && (!d_base || !d_tail_offs || !d_lens || !d_pads || !d_states || !d_digests || !d_roots || !d_exp_sha1 ||
+              !d_exp_roots || !d_flags || !d_matched))
+        return fail(VX_EINVAL, "vx_tuning_hybrid_finish_kernel: NULL argument");
+    if (padded_total == 0 || (padded_total & 63))
+        return fail(VX_EINVAL, "vx_tuning_hybrid_finish_kernel: padded_total must be a multiple of 64");
+    hipError_t e = vx::launch_hybrid_finish(static_cast<const uint8_t*>(d_base), d_tail_offs, d_lens, d_pads, n,
+                                            padded_total, d_states, static_cast<uint8_t*>(d_digests),
+                                            static_cast<const uint8_t*>(d_roots),
+                                            static_cast<const uint8_t*>(d_exp_sha1),
+                                            static_cast<const uint8_t*>(d_exp_roots), d_exp_index, d_flags,
+                                            static_cast<uint8_t*>(d_matched), static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : hip_fail(e, "vx_tuning_hybrid_finish_kernel");
 }
 
 int64_t vx_hybrid_hash_files_range(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
