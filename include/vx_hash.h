@@ -288,6 +288,47 @@ typedef struct vx_verify_round {
  * many rounds the call had. */
 int64_t vx_last_verify_rounds(const vx_ctx* ctx, vx_verify_round* out, size_t max);
 
+/* ---- skipping file holes in the re-verify -------------
+ * The reference re-verifies right after it has fallocated every file to its
+ * torrent length (file_store.rs:22-43, :146; torrent.rs:716-761), so what a
+ * resume reads is mostly ranges no one ever wrote.  With on = 1 (default 0:
+ * every call as before, nothing scanned) vx_verify_files, _range and _multi
+ * and vx_merkle_verify_files and _range first ask the file system for each
+ * opened file's data extents (lseek SEEK_DATA / SEEK_HOLE, at most 65,536 per
+ * file; what lies beyond them is data) and judge what was never written
+ * without reading it:
+ *   v1  a piece whose every segment lies wholly in holes is not read, staged
+ *       or copied; matched_out[i] = (expected row == SHA-1 of its length in
+ *       zero bytes), that digest made once per context and length on the GPU.
+ *       A piece only partly in holes is read whole, as before.
+ *   v2  a 16 KiB block wholly in a hole is not read; its leaf row is the
+ *       SHA-256 of its length in zero bytes, made on the GPU from nothing.  A
+ *       piece's other blocks are read as before.
+ * A byte is a hole byte iff it lies below min(st_size, the file's torrent
+ * length) and in no data extent: bytes past the end of a short file are
+ * missing, not holes, so such a file fails the pieces it fails with the setting
+ * off, and the return value counts them the same.  A file that did not open
+ * has no holes; an lseek error other than ENXIO makes its whole file data.
+ * Verdicts, return values and vx_get_stats are those of the setting off (hole
+ * pieces count as completed, by their bytes, and as mismatched when they are);
+ * vx_last_verify's read_bytes counts only what was read.
+ * vx_verify_files_split (the pool claims pieces the engine cannot pre-judge),
+ * the hybrid calls and the three *_hash_files calls (a torrent is not created
+ * from unwritten files) ignore the setting.  VX_EINVAL: NULL ctx, on not 0/1. */
+int vx_set_skip_holes(vx_ctx* ctx, int on);
+/* What the last vx_verify_files / vx_merkle_verify_files (or _range) call on
+ * ctx skipped; all zero when the setting was off. */
+typedef struct vx_hole_trace {
+    uint64_t hole_pieces; /* v1: pieces judged without a read                      */
+    uint64_t hole_blocks; /* v2: 16 KiB blocks hashed from nothing                 */
+    uint64_t hole_bytes;  /* their bytes: not read, staged or copied               */
+    uint64_t extents;     /* data extents the scan found, over all files           */
+    double scan_ms;       /* the lseek scan and the classification                 */
+    double zero_hash_ms;  /* GPU time of the zero hashes this call had to make
+                             (0: every one came from the context's cache)          */
+} vx_hole_trace;
+int vx_last_verify_holes(const vx_ctx* ctx, vx_hole_trace* out);
+
 /* ---- synchronous host batches (bulk re-verify, torrent.rs:724-740) ----- */
 /* digests_out: n*20 bytes.  Pieces are pipelined through the slots, longest
  * first (ragged batches: DESIGN.md §6.4); outputs are always in the caller's
@@ -482,6 +523,11 @@ int vx_sha1_device_ragged(const void* d_base, const uint64_t* d_offsets, const u
 int vx_sha1_device_ragged_hint(const void* d_base, const uint64_t* d_offsets, const uint32_t* d_lens,
                                const uint32_t* d_order, uint32_t n, uint32_t max_len, uint64_t total_len,
                                void* d_digests, const void* d_expected, void* d_matched, void* stream);
+/* d_digests[20*j..] = SHA-1 of d_lens[j] zero bytes, j in [0,n): hashed from
+ * nothing, no input is read but d_lens (4-byte aligned, as d_digests).  The
+ * digest an unwritten piece's expected row is compared with (vx_set_skip_holes).
+ * Enqueue-only; n == 0 launches nothing. */
+int vx_sha1_device_zeros(const uint32_t* d_lens, uint32_t n, void* d_digests, void* stream);
 /* Host helper: write into order_out the permutation that sorts lens[0..n)
  * by descending length (stable).  Used to build d_order. */
 int vx_sort_order(const uint32_t* lens, uint32_t n, uint32_t* order_out);
@@ -609,6 +655,12 @@ int vx_merkle_device_blocks(const void* d_stage, const uint32_t* d_rows, const u
  * 2^d_log2w[i] slots (NULL: log2_width).  roots / expected / matched as for vx_merkle_device_ragged. */
 int vx_merkle_device_nodes(const void* d_leaves, const uint8_t* d_log2w, uint32_t n, uint32_t log2_width,
                            void* d_roots, const void* d_expected, void* d_matched, void* stream);
+/* Leaf rows of unwritten blocks: row j of d_leaves (16-byte aligned) =
+ * SHA-256 of d_lens[j] zero bytes, hashed from nothing.  d_lens[j] in
+ * 1..VX_MERKLE_BLOCK is device-resident and not checked here;
+ * vortex_amd.device.merkle_zero_leaves checks it.  Enqueue-only; n == 0
+ * launches nothing. */
+int vx_merkle_device_zero_leaves(const uint32_t* d_lens, uint32_t n, void* d_leaves, void* stream);
 
 /* Re-verify a v2 torrent's files from disk: the v2 counterpart of
  * vx_verify_files.  Layout (BEP 52): every file starts its own pieces and no

@@ -10,6 +10,7 @@ Modules
   hash_pool  HashPool / DownloadedPiece / verify_pieces (reference names)
   device     device-resident batches on torch tensors (the hot path)
   merkle     BitTorrent v2 piece geometry on the host (file_pieces, pad_hash)
+  sparse     which parts of the files were never written (the os.lseek model of skip_holes)
   _lib       ctypes binding (fails loudly when the library is missing)
 """
 from ._lib import LIB_PATH, VxError, lib  # noqa: F401

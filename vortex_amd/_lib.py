@@ -63,6 +63,7 @@ EXPORTS = (
     "vx_merkle_tree_proof", "vx_merkle_tree_layout",
     "vx_hash_files", "vx_hash_files_range", "vx_merkle_hash_files", "vx_merkle_hash_files_range",
     "vx_hybrid_hash_files", "vx_hybrid_hash_files_range",
+    "vx_set_skip_holes", "vx_last_verify_holes", "vx_sha1_device_zeros", "vx_merkle_device_zero_leaves",
 )
 # ... plus include/vx_tuning.h and include/vx_synth.h: libvortex_amd_tuning.so only.
 TUNING_EXPORTS = (
@@ -190,6 +191,12 @@ class vx_verify_trace(ctypes.Structure):
         ("chunk_bytes", ctypes.c_uint64)]
 
 
+class vx_hole_trace(ctypes.Structure):
+    """What the last file re-verify skipped (vx_last_verify_holes): 48 bytes."""
+    _fields_ = [(name, ctypes.c_uint64) for name in ("hole_pieces", "hole_blocks", "hole_bytes", "extents")] + [
+        ("scan_ms", ctypes.c_double), ("zero_hash_ms", ctypes.c_double)]
+
+
 VX_ROUND_NEW_WINDOW, VX_ROUND_HEAD_RAMP, VX_ROUND_TAIL_RAMP = 1, 2, 4
 
 
@@ -249,6 +256,10 @@ def _declare(L: ctypes.CDLL, tuning: bool = False) -> None:
         "vx_sort_order": ([vp, c.c_uint32, vp], c.c_int),
         "vx_last_verify": ([vp, c.POINTER(vx_verify_trace)], c.c_int),
         "vx_last_verify_rounds": ([vp, c.POINTER(vx_verify_round), c.c_size_t], c.c_int64),
+        "vx_set_skip_holes": ([vp, c.c_int], c.c_int),
+        "vx_last_verify_holes": ([vp, c.POINTER(vx_hole_trace)], c.c_int),
+        "vx_sha1_device_zeros": ([vp, c.c_uint32, vp, vp], c.c_int),
+        "vx_merkle_device_zero_leaves": ([vp, c.c_uint32, vp, vp], c.c_int),
         "vx_plan_verify": ([c.c_uint64, c.c_uint32, c.c_uint64, c.c_uint32, c.c_double, c.POINTER(vx_plan)], c.c_int),
         "vx_plan_verify_gpus": ([c.c_uint64, c.c_uint32, c.c_uint64, c.c_uint32, c.c_double, c.c_uint32,
                                  c.POINTER(vx_plan)], c.c_int),

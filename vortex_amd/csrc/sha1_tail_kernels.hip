@@ -21,6 +21,10 @@
 // The zero-block loop runs to the wave's largest Z; lanes that are done keep
 // their state under a select.  Lanes past n, and lanes whose pad_len is 0 (an
 // unpadded piece ends in the chunked kernel), store nothing.
+//
+// The same zero-block round hashes whole zero pieces from nothing
+// (sha1_zero_kernel at the end of this file): the digests the
+// file re-verify compares unwritten pieces' expected rows with.
 #include "sha1_device.hpp"
 #include "vx_kernels.h"
 
@@ -319,6 +323,59 @@ hipError_t launch_hybrid_merge(const uint8_t* v1, const uint8_t* v2, uint32_t n,
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(hybrid_merge_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, v1, v2, n,
                        matched);
+    return hipGetLastError();
+}
+
+// SHA-1 of lens[j] zero bytes, from nothing: the digest the
+// file re-verify compares an unwritten piece's expected row with, so no byte
+// of such a piece is read, staged or copied.  Lane j runs lens[j] >> 6 blocks
+// through the tail kernel's zero-block round (to the wave's largest count,
+// lanes that are done keep their state under a select), then builds its last
+// one or two blocks in registers (lens[j] & 63 zeros, 0x80, the bit length)
+// for the general compression: the length need not be a multiple of 64 here,
+// so there is no launch-wide final schedule.  Nothing is loaded but lens[j];
+// lanes past n redo lane n - 1 (in bounds) and store nothing.
+__global__ __launch_bounds__(kTailBlock) void sha1_zero_kernel(const uint32_t* __restrict__ lens, uint32_t n,
+                                                               uint8_t* __restrict__ digests) {
+    const uint32_t j = blockIdx.x * kTailBlock + threadIdx.x;
+    const uint32_t len = lens[j < n ? j : n - 1];
+    const uint32_t z = len >> 6, rem = len & 63u;
+    const uint32_t z_wave = __builtin_amdgcn_readfirstlane(tail_wave_max(z));
+
+    State s = iv();
+    for (uint32_t b = 0; b < z_wave; ++b) {
+        State t = s;
+        compress_known(t, ZeroWords{});
+        const bool mine = b < z;
+        s.h0 = mine ? t.h0 : s.h0;
+        s.h1 = mine ? t.h1 : s.h1;
+        s.h2 = mine ? t.h2 : s.h2;
+        s.h3 = mine ? t.h3 : s.h3;
+        s.h4 = mine ? t.h4 : s.h4;
+    }
+    uint32_t w[16];
+#pragma unroll
+    for (uint32_t k = 0; k < 16; ++k) w[k] = k == (rem >> 2) ? 0x80000000u >> (8u * (rem & 3u)) : 0u;
+    const uint32_t bits_hi = len >> 29, bits_lo = len << 3;
+    if (rem <= 55) {  // (0x80 lies in words 0..13: the length's two words are free)
+        w[14] = bits_hi;
+        w[15] = bits_lo;
+    }
+    compress(s, w);
+    if (rem > 55) {
+#pragma unroll
+        for (int k = 0; k < 14; ++k) w[k] = 0;
+        w[14] = bits_hi;
+        w[15] = bits_lo;
+        compress(s, w);
+    }
+    if (j < n) tail_emit(s, j, digests, nullptr, nullptr);
+}
+
+hipError_t launch_sha1_zeros(const uint32_t* lens, uint32_t n, uint8_t* digests, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(sha1_zero_kernel, dim3((n + kTailBlock - 1) / kTailBlock), dim3(kTailBlock), 0, stream, lens, n,
+                       digests);
     return hipGetLastError();
 }
 

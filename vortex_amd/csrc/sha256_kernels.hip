@@ -882,4 +882,78 @@ hipError_t launch_merkle_proofs(const uint8_t* hashes, const vx_merkle_proof* pr
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Leaf rows of unwritten blocks (the re-verify from disk over file holes,
+// DESIGN.md §6.11): lane j writes SHA-256(lens[j] zero bytes), lens[j] in
+// 1..16384, to leaf row rows[j] (NULL: row j).  Nothing is read but the two
+// tables.  A full block's row is the same for every lane, so the caller passes
+// it by value once it has it (have_full; made by this kernel with n = 1) and
+// such a lane only stores; any other lane hashes from nothing: every schedule
+// word of an all-zero block is zero, so a block is its 64 rounds with K[t]
+// alone, run to the wave's largest block count under a select, and the last
+// one or two blocks (zeros, 0x80, the bit length) take the general compression.
+namespace {
+
+constexpr sha256::ConstBlock zero_block() {  // K[t] + W[t] of an all-zero block: K[t]
+    sha256::ConstBlock b{};
+    for (int t = 0; t < 64; ++t) b.kw[t] = sha256::kK[t];
+    return b;
+}
+__device__ constexpr sha256::ConstBlock kZeroBlock = zero_block();
+
+__global__ __launch_bounds__(kBlock) void merkle_zero_leaf_kernel(const uint32_t* __restrict__ rows,
+                                                                  const uint32_t* __restrict__ lens, uint32_t n,
+                                                                  uint8_t* __restrict__ leaves, const uint4 full_lo,
+                                                                  const uint4 full_hi, const uint32_t have_full) {
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t jj = j < n ? j : n - 1;  // lanes past n redo lane n-1 (in bounds) and store nothing
+    const uint32_t len = lens[jj];
+    const uint32_t row = rows ? rows[jj] : jj;
+    const bool known = have_full && len == kLeaf;
+    const uint32_t z = known ? 0u : len >> 6, rem = len & 63u;
+    const uint32_t z_wave = __builtin_amdgcn_readfirstlane(wave_max(z));
+    State s = sha256::iv();
+    for (uint32_t b = 0; b < z_wave; ++b) {
+        State t = s;
+        sha256::compress_const(t, kZeroBlock);
+        const bool mine = b < z;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s.h[k] = mine ? t.h[k] : s.h[k];
+    }
+    if (__builtin_amdgcn_readfirstlane(wave_max(known ? 0u : 1u))) {  // wave-uniform: some lane hashes
+        uint32_t w[16];
+#pragma unroll
+        for (uint32_t k = 0; k < 16; ++k) w[k] = k == (rem >> 2) ? 0x80000000u >> (8u * (rem & 3u)) : 0u;
+        if (rem <= 55) w[15] = len << 3;  // a leaf is at most 16 KiB: the high word stays 0
+        sha256::compress(s, w);
+        if (rem > 55) {
+#pragma unroll
+            for (int k = 0; k < 15; ++k) w[k] = 0;
+            w[15] = len << 3;
+            sha256::compress(s, w);
+        }
+    }
+    if (j >= n) return;
+    if (known) {
+        uint4* o = reinterpret_cast<uint4*>(leaves + (size_t)row * 32);
+        o[0] = full_lo;
+        o[1] = full_hi;
+    } else {
+        store_row(leaves, row, s);
+    }
+}
+
+}  // namespace
+
+hipError_t launch_merkle_zero_leaves(const uint32_t* rows, const uint32_t* lens, uint32_t n, uint8_t* leaves,
+                                     const uint8_t* full_row, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    uint4 full[2] = {};  // rows are bytes: the words as the device stores them
+    if (full_row) memcpy(full, full_row, 32);
+    const uint32_t grid = (uint32_t)(((uint64_t)n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(merkle_zero_leaf_kernel, dim3(grid), dim3(kBlock), 0, stream, rows, lens, n, leaves, full[0],
+                       full[1], full_row ? 1u : 0u);
+    return hipGetLastError();
+}
+
 }  // namespace vx

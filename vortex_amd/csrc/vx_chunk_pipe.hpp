@@ -69,6 +69,10 @@ struct ChunkPipe {
     // separate `copied` marker (each marker between two copies on one stream
     // costs the copy engine ~15 us; 36 rounds of 8 MiB pieces add up).
     hipEvent_t copy_end = nullptr;
+    // Set (the file re-verify over file holes): hole[i] != 0
+    // marks a row no round hashes.  Its verdict byte is not the kernel's (the
+    // caller overwrites it) and it is not counted here: the caller counts it.
+    const uint8_t* hole = nullptr;
 
     explicit ChunkPipe(vx_ctx* ctx) : c(ctx) {}
 
@@ -205,9 +209,10 @@ struct ChunkPipe {
             c->stats.bytes_completed += bytes;
             for (const auto& r : rows) {
                 c->stats.pieces_completed += r.second - r.first;
+                for (uint64_t i = r.first; i < r.second && hole; ++i) c->stats.pieces_completed -= hole[i] != 0;
                 if (matched_out && d_match)
                     for (uint64_t i = r.first; i < r.second; ++i)
-                        c->stats.pieces_mismatched += matched_out[i] == 0 && !(bad && bad[i]);
+                        c->stats.pieces_mismatched += matched_out[i] == 0 && !(bad && bad[i]) && !(hole && hole[i]);
             }
         }
         wait_and_free_inflight(c);

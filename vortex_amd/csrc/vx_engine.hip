@@ -604,6 +604,7 @@ int vx_destroy(vx_ctx* c) {
         if (m.h) (void)hipHostFree(m.h);
     }
     free_merkle_files(c);
+    free_holes(c);
     if (c->mfiles.chain) (void)hipEventDestroy(c->mfiles.chain);
     if (c->chunk_prev) (void)hipEventDestroy(c->chunk_prev);
     for (hipEvent_t e : c->copy_ev)

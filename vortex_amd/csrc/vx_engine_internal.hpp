@@ -26,6 +26,7 @@
 #include <thread>
 #include <vector>
 
+#include "vx_extents.hpp"
 #include "vx_files.hpp"
 #include "vx_hash.h"
 #include "vx_hybrid_slot.hpp"
@@ -314,6 +315,28 @@ struct vx_ctx {
         hipEvent_t chain = nullptr;
     } mfiles;
     uint64_t verify_t0_ns = 0;                // the running re-verify call's start (steady clock)
+    // Skipping file holes in the re-verify (vx_set_skip_holes, DESIGN.md
+    // §6.11): the setting, the last call's trace, and what the zero hashes need,
+    // all made on first use: a stream of their own with two timing events, a
+    // pinned block h and a device block d (kZeroBlock bytes each: 2 lengths |
+    // 2 SHA-1 digests | one leaf row), the SHA-1 digests of zero pieces by
+    // length (at most kZeroCache, the oldest dropped first) and the leaf row of
+    // a full zero block.
+    struct Holes {
+        static constexpr size_t kZeroBlock = 128, kDigestsAt = 16, kLeafAt = 64, kZeroCache = 64;
+        int skip = 0;
+        vx_hole_trace last{};
+        hipStream_t stream = nullptr;
+        hipEvent_t t0 = nullptr, t1 = nullptr;
+        uint8_t *h = nullptr, *d = nullptr;
+        struct Sha1Zero {
+            uint32_t len;
+            uint8_t digest[VX_DIGEST_LEN];
+        };
+        std::vector<Sha1Zero> sha1_zero;
+        uint8_t zero_leaf[VX_SHA256_LEN] = {};
+        bool have_zero_leaf = false;
+    } holes;
 };
 
 namespace vxe {
@@ -415,6 +438,13 @@ inline int64_t end_files_call(vx_ctx* c, const std::vector<int>& fds, const std:
     c->stats.io_errors += (uint64_t)nbad;
     return nbad;
 }
+// Skipping file holes (vx_reverify.hip).  ensure_holes: the zero hashes'
+// stream, events and blocks.  scan_holes: the files' extents when the setting
+// is on (else an empty set, nothing scanned), counted and timed into the
+// call's hole trace, which it resets.  free_holes: vx_destroy's part.
+int ensure_holes(vx_ctx* c, const char* who);
+vx_extents::Holes scan_holes(vx_ctx* c, const std::vector<int>& fds, const uint64_t* file_lengths);
+void free_holes(vx_ctx* c);
 void free_merkle_files(vx_ctx* c);  // vx_merkle.hip: vx_merkle_verify_files' buffers, not its event
 // vx_merkle.hip, the end of a v2 or hybrid hash call: the layer trees of every
 // non-empty file (vx_merkle_tree_layout) from d_rows, the whole torrent's piece

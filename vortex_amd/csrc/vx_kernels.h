@@ -95,6 +95,9 @@ hipError_t launch_hybrid_prep(const uint64_t* offsets, const uint32_t* lens, con
                               hipStream_t stream);
 hipError_t launch_hybrid_merge(const uint8_t* v1, const uint8_t* v2, uint32_t n, uint8_t* matched,
                                hipStream_t stream);
+// SHA-1 of lens[j] zero bytes into digests row j, nothing read but lens
+// (sha1_zero_kernel); digests 4-byte aligned.
+hipError_t launch_sha1_zeros(const uint32_t* lens, uint32_t n, uint8_t* digests, hipStream_t stream);
 
 // The end of a hybrid download slot (hybrid_finish_kernel):
 // lane j finishes piece j when pads[j] != 0 (as launch_zero_tail with pids =
@@ -164,6 +167,12 @@ hipError_t launch_merkle_blocks(const uint8_t* stage, const uint32_t* rows, cons
                                 uint8_t* leaves, hipStream_t stream);
 hipError_t launch_merkle_nodes(const uint8_t* leaves, const uint8_t* log2w, uint32_t n, uint32_t log2_width,
                                uint8_t* roots, const uint8_t* expected, uint8_t* matched, hipStream_t stream);
+// Leaf rows of unwritten blocks (merkle_zero_leaf_kernel):
+// SHA-256 of lens[j] (1..16384) zero bytes into leaf row rows[j] (NULL: j),
+// nothing read but the tables.  full_row (host, 32 bytes, may be NULL): the row
+// of a full 16 KiB block, stored as is where lens[j] == 16384.
+hipError_t launch_merkle_zero_leaves(const uint32_t* rows, const uint32_t* lens, uint32_t n, uint8_t* leaves,
+                                     const uint8_t* full_row, hipStream_t stream);
 // Root of a layer of n >= 1 hashes; pads[k] = the pad hash of the layer's
 // height + k (one per level to the root); work: 32*n bytes.
 hipError_t launch_merkle_root(const uint8_t* layer, uint32_t n, uint8_t* work, uint8_t* root,

@@ -424,6 +424,17 @@ int vx_merkle_device_nodes(const void* d_leaves, const uint8_t* d_log2w, uint32_
     return 0;
 }
 
+int vx_merkle_device_zero_leaves(const uint32_t* d_lens, uint32_t n, void* d_leaves, void* stream) {
+    if (n == 0) return 0;
+    if (!d_lens || !d_leaves) return fail(VX_EINVAL, "vx_merkle_device_zero_leaves: NULL argument");
+    if ((reinterpret_cast<uintptr_t>(d_lens) & 3) || (reinterpret_cast<uintptr_t>(d_leaves) & 15))
+        return fail(VX_EINVAL, "vx_merkle_device_zero_leaves: d_lens must be 4-byte and d_leaves 16-byte aligned");
+    hipError_t e = vx::launch_merkle_zero_leaves(nullptr, d_lens, n, static_cast<uint8_t*>(d_leaves), nullptr,
+                                                 static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "merkle zero leaf kernel launch");
+    return 0;
+}
+
 // ---- vx_merkle_verify_files: the v2 re-verify from disk ----
 // Rounds of 16 KiB blocks packed by vx_merkle::Rounds, one slot's pinned stage
 // each.  Per round, on the slot's stream: the data H2D, the rows | lens table
@@ -469,6 +480,33 @@ static int ensure_merkle_files(vx_ctx* c, uint64_t window_rows, uint64_t entries
         if (hipMalloc(&m.d_call, cap * 34) != hipSuccess) return fail(VX_ENOMEM, oom);
         m.call_cap = cap;
     }
+    return 0;
+}
+
+// The leaf row of a full unwritten block, made once per
+// context by the zero-leaf kernel itself with n = 1 (there is no host SHA-256)
+// and passed to every later launch by value.
+static int zero_leaf_row(vx_ctx* c) {
+    vx_ctx::Holes& h = c->holes;
+    if (h.have_zero_leaf) return 0;
+    int rc = ensure_holes(c, "vx_merkle_verify_files");
+    if (rc) return rc;
+    const uint32_t len = VX_MERKLE_BLOCK;
+    std::memcpy(h.h, &len, sizeof(len));
+    hipError_t e = hipMemcpyAsync(h.d, h.h, sizeof(len), hipMemcpyHostToDevice, h.stream);
+    if (e == hipSuccess) e = hipEventRecord(h.t0, h.stream);
+    if (e == hipSuccess)
+        e = vx::launch_merkle_zero_leaves(nullptr, reinterpret_cast<const uint32_t*>(h.d), 1, h.d + h.kLeafAt, nullptr,
+                                          h.stream);
+    if (e == hipSuccess) e = hipEventRecord(h.t1, h.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h.h + h.kLeafAt, h.d + h.kLeafAt, 32, hipMemcpyDeviceToHost, h.stream);
+    const hipError_t sync = hipStreamSynchronize(h.stream);
+    if (e != hipSuccess || sync != hipSuccess)
+        return hip_fail(e != hipSuccess ? e : sync, "vx_merkle_verify_files: zero leaf row");
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, h.t0, h.t1) == hipSuccess) h.last.zero_hash_ms = ms;
+    std::memcpy(h.zero_leaf, h.h + h.kLeafAt, 32);
+    h.have_zero_leaf = true;
     return 0;
 }
 
@@ -530,6 +568,16 @@ static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint
     const int nthreads = io_threads ? (int)io_threads : (int)std::max(1u, std::min(16u, usable_cpus()));
     std::vector<uint8_t> bad(count, 0);
     if (matched_out) std::memset(matched_out, 0, count);
+    // Blocks that lie wholly in file holes are not read: the
+    // packer leaves them out of the stage and a kernel of their own writes
+    // their leaf rows.  The hash call does not ask.
+    c->holes.last = vx_hole_trace{};
+    const vx_extents::Holes holes = hashing ? vx_extents::Holes() : scan_holes(c, fds, file_lengths);
+    vx_merkle::HolePredicate in_hole;
+    if (holes.any()) {
+        in_hole = [&holes](uint32_t f, uint64_t off, uint32_t len) { return holes.hole(f, (int64_t)off, len); };
+        if ((rc = zero_leaf_row(c))) return end_files_call(c, fds, bad, t_call, rc);
+    }
     const size_t nslots = c->slots.size();
     // Reads run ahead as far as the slots allow: a v2 round carries no state,
     // so a slot is free again as soon as its own round's kernels are done, and
@@ -542,7 +590,8 @@ static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint
         const std::vector<vx_files::FileSpan> no_spans;
         const vx_files::DirectIo dio(fds, c->cfg.direct_io != 0);
         vx_files::Readers rd(nthreads, no_spans, fds, piece_length, bad.data(), first, &dio, true);
-        vx_merkle::Rounds pack(file_lengths, nfiles, piece_length, first, count, bpr, R, entries, kMerkleRunBlocks);
+        vx_merkle::Rounds pack(file_lengths, nfiles, piece_length, first, count, bpr, R, entries, kMerkleRunBlocks,
+                               in_hole);
         std::vector<vx_merkle::Round> round(nslots);
         std::vector<std::vector<vx_files::ReadItem>> items(nslots);
         std::vector<uint64_t> ticket(nslots, 0);
@@ -580,13 +629,15 @@ static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint
             Slot& s = c->slots[si];
             const vx_merkle::Round& r = round[si];
             rd.wait(ticket[si]);
-            const uint32_t m = (uint32_t)r.rows.size();
+            // the tables: rows | lens, each the block kernel's m entries, then the hole blocks'
+            const uint32_t all = (uint32_t)r.rows.size(), m = all - r.hole_blocks;
             uint32_t* h_tab = mf.h_tab[si];
             uint32_t* d_tab = mf.d_tab[si];
-            std::memcpy(h_tab, r.rows.data(), (size_t)m * 4);
-            std::memcpy(h_tab + m, r.lens.data(), (size_t)m * 4);
-            hipError_t e = hipMemcpyAsync(s.d_arena, s.h_stage, r.bytes, hipMemcpyHostToDevice, s.stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_tab, h_tab, (size_t)m * 8, hipMemcpyHostToDevice, s.stream);
+            std::memcpy(h_tab, r.rows.data(), (size_t)all * 4);
+            std::memcpy(h_tab + all, r.lens.data(), (size_t)all * 4);
+            hipError_t e = hipSuccess;
+            if (r.bytes) e = hipMemcpyAsync(s.d_arena, s.h_stage, r.bytes, hipMemcpyHostToDevice, s.stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_tab, h_tab, (size_t)all * 8, hipMemcpyHostToDevice, s.stream);
             if (e == hipSuccess && have_prev) e = hipStreamWaitEvent(s.stream, mf.chain, 0);
 #ifdef VX_TEST_HOOKS
             if (e == hipSuccess && c->fail_launch_after >= 0 && c->fail_launch_after-- == 0) {
@@ -594,7 +645,11 @@ static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint
                 break;
             }
 #endif
-            if (e == hipSuccess) e = vx::launch_merkle_blocks(s.d_arena, d_tab, d_tab + m, m, mf.d_window, s.stream);
+            if (e == hipSuccess && m)
+                e = vx::launch_merkle_blocks(s.d_arena, d_tab, d_tab + all, m, mf.d_window, s.stream);
+            if (e == hipSuccess && r.hole_blocks)
+                e = vx::launch_merkle_zero_leaves(d_tab + m, d_tab + all + m, r.hole_blocks, mf.d_window,
+                                                  c->holes.zero_leaf, s.stream);
             for (const vx_merkle::Nodes& g : r.nodes) {
                 if (e != hipSuccess) break;
                 const uint64_t k = g.first - first;
@@ -613,6 +668,8 @@ static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint
             ++n_rounds;
             n_bytes += r.file_bytes;
             copy_bytes += r.bytes;
+            c->holes.last.hole_blocks += r.hole_blocks;
+            c->holes.last.hole_bytes += r.hole_bytes;
             t_last_enqueue = clk::now();
         }
         rd.wait();  // error path: no read may still target a stage

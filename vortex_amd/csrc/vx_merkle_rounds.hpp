@@ -14,6 +14,11 @@
 //    the data blocks, one entry of length 0 per absent slot (a slot of a
 //    piece's tree beyond its last block) of the pieces the round finished;
 //  * the node launches: the groups of pieces the round finished.
+// With a hole predicate a block the file system never wrote
+// gets no read and no stage block: it becomes an entry (row, length) in a third
+// section of the tables, behind the data blocks and the absent slots, whose
+// leaf row is SHA-256(length zero bytes) by a kernel of its own.  Window and
+// group rules count its row like any row.
 //
 // Leaf rows live in a ring of `window_rows` rows (a power of two).  The node
 // kernels reduce pieces laid out piece-major at one width per launch, so the
@@ -33,6 +38,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <functional>
 #include <vector>
 
 namespace vx_merkle {
@@ -122,31 +128,39 @@ struct Nodes {
 
 struct Round {
     std::vector<Read> reads;
-    std::vector<uint32_t> rows, lens;  // data_blocks entries for the stage's blocks, then the absent slots
+    // data_blocks entries for the stage's blocks, then the absent slots, then hole_blocks entries for the hole blocks
+    std::vector<uint32_t> rows, lens;
     uint32_t data_blocks = 0;
+    uint32_t hole_blocks = 0;
     uint64_t bytes = 0;  // the stage's extent: what the data copy moves
-    uint64_t file_bytes = 0;
+    uint64_t file_bytes = 0;  // the blocks' bytes, read or not
+    uint64_t hole_bytes = 0;  // ... of them, the hole blocks'
     std::vector<Nodes> nodes;
     void clear() {
         reads.clear();
         rows.clear();
         lens.clear();
         nodes.clear();
-        data_blocks = 0;
-        bytes = file_bytes = 0;
+        data_blocks = hole_blocks = 0;
+        bytes = file_bytes = hole_bytes = 0;
     }
 };
+
+// (file, offset in it, length): the whole block was never written.
+using HolePredicate = std::function<bool(uint32_t, uint64_t, uint32_t)>;
 
 class Rounds {
   public:
     // Pieces [first, first + count) of the torrent; a round holds at most
     // blocks_per_round stage blocks and max_entries table entries (at least
     // blocks_per_round + piece_length / 16 KiB, so an empty round takes any
-    // piece's end); a read is at most max_run_blocks long.
+    // piece's end); a read is at most max_run_blocks long.  hole (may be empty):
+    // the blocks to leave unread.
     Rounds(const uint64_t* file_lengths, size_t nfiles, uint32_t piece_length, uint64_t first, uint64_t count,
-           uint32_t blocks_per_round, uint32_t window_rows, uint32_t max_entries, uint32_t max_run_blocks)
+           uint32_t blocks_per_round, uint32_t window_rows, uint32_t max_entries, uint32_t max_run_blocks,
+           HolePredicate hole = nullptr)
         : cur_(file_lengths, nfiles, piece_length), end_(first + count), bpr_(blocks_per_round), R_(window_rows),
-          max_entries_(max_entries), max_run_(std::max<uint32_t>(1, max_run_blocks)) {
+          max_entries_(max_entries), max_run_(std::max<uint32_t>(1, max_run_blocks)), hole_(std::move(hole)) {
         cur_.seek(first);
     }
 
@@ -161,6 +175,8 @@ class Rounds {
     bool next(Round& r) {
         r.clear();
         absent_.clear();
+        hole_rows_.clear();
+        hole_lens_.clear();
         if (cur_.end() || cur_.index >= end_) return false;
         uint64_t live_lo = open_ ? g_base_ : 0;
         bool have_lo = open_;
@@ -183,16 +199,33 @@ class Rounds {
                 open_ = true;
             }
             const uint32_t nb = cur_.blocks();
-            const uint32_t take = std::min<uint32_t>(nb - blk_, bpr_ - r.data_blocks);
+            const uint64_t plen = cur_.len();
+            // the blocks that fit: to the piece's end, or to the first data block the stage has no room for
+            uint32_t take = std::min<uint32_t>(nb - blk_, bpr_ - r.data_blocks);
+            if (hole_) {
+                uint32_t room = bpr_ - r.data_blocks;
+                for (take = 0; blk_ + take < nb; ++take) {
+                    const uint64_t at = (uint64_t)(blk_ + take) * kBlock;
+                    if (is_hole(at, plen)) continue;
+                    if (room == 0) break;
+                    --room;
+                }
+            }
             const bool completes = blk_ + take == nb;
             const uint64_t absent = completes ? (1ull << cur_.log2w()) - nb : 0;
-            const uint64_t entries = r.rows.size() + absent_.size();
+            const uint64_t entries = r.rows.size() + absent_.size() + hole_rows_.size();
             if (entries && entries + take + absent > max_entries_) break;  // the tables: cut here
             const uint64_t piece_row = g_base_ + ((cur_.index - g_first_) << g_K_);
-            const uint64_t plen = cur_.len();
             for (uint32_t k = 0; k < take; ++k) {
                 const uint64_t at = (uint64_t)(blk_ + k) * kBlock;
                 const uint32_t len = (uint32_t)std::min<uint64_t>(kBlock, plen - at);
+                if (hole_ && is_hole(at, plen)) {
+                    hole_rows_.push_back(ring(piece_row + blk_ + k));
+                    hole_lens_.push_back(len);
+                    r.file_bytes += len;
+                    r.hole_bytes += len;
+                    continue;
+                }
                 add_read(r, (uint32_t)cur_.f, cur_.off() + at, len, cur_.index);
                 r.rows.push_back(ring(piece_row + blk_ + k));
                 r.lens.push_back(len);
@@ -212,11 +245,19 @@ class Rounds {
         }
         r.rows.insert(r.rows.end(), absent_.begin(), absent_.end());
         r.lens.insert(r.lens.end(), absent_.size(), 0u);
+        r.rows.insert(r.rows.end(), hole_rows_.begin(), hole_rows_.end());
+        r.lens.insert(r.lens.end(), hole_lens_.begin(), hole_lens_.end());
+        r.hole_blocks = (uint32_t)hole_rows_.size();
         return true;
     }
 
   private:
     uint32_t ring(uint64_t row) const { return (uint32_t)(row & (R_ - 1)); }
+
+    // the block at byte `at` of the current piece (plen bytes)
+    bool is_hole(uint64_t at, uint64_t plen) const {
+        return hole_((uint32_t)cur_.f, cur_.off() + at, (uint32_t)std::min<uint64_t>(kBlock, plen - at));
+    }
 
     void form_group(uint64_t& n, uint64_t& K) const {
         PieceCursor lk = cur_;
@@ -266,6 +307,8 @@ class Rounds {
     uint64_t g_first_ = 0, g_n_ = 0, g_base_ = 0, g_done_ = 0, alloc_ = 0;
     uint32_t g_K_ = 0;
     std::vector<uint32_t> absent_;
+    const HolePredicate hole_;
+    std::vector<uint32_t> hole_rows_, hole_lens_;
 };
 
 }  // namespace vx_merkle

@@ -9,11 +9,78 @@
 // continues each piece's 20-byte SHA-1 state from round k-1, so PCIe moves
 // round k+1 while the GPU compresses round k and no launch waits on a whole
 // multi-MiB chain.  Completions are consumed here; they never reach vx_poll.
+// With vx_set_skip_holes, pieces that lie wholly in ranges the file system
+// never wrote are left out of both paths and judged against the SHA-1 of zeros
+// (vx_extents.hpp).
 #include "vx_chunk_pipe.hpp"
 
 using namespace vxe;
 
 namespace {
+
+// The SHA-1 digests of zero pieces a call over file holes compares expected
+// rows with: at most two lengths per call, the torrent's
+// piece length and its last piece's.  start() launches sha1_zero_kernel for the
+// lengths the context has not cached, on the holes' own stream, so the chain (a
+// 2 MiB piece: 32,768 blocks, ~24 ms) runs beside the call's reads, copies and
+// kernels; wait() takes the digests into the cache.  No host hashing: the
+// product has none.
+struct ZeroDigests {
+    vx_ctx* c;
+    vx_ctx::Holes::Sha1Zero have[2] = {};  // the call's lengths: cached ones first, then [n_have, n_have + n) launched
+    int n_have = 0, n = 0;
+
+    explicit ZeroDigests(vx_ctx* ctx) : c(ctx) {}
+    const uint8_t* get(uint32_t len) const {
+        for (int k = 0; k < n_have; ++k)
+            if (have[k].len == len) return have[k].digest;
+        return nullptr;
+    }
+    int start(const uint32_t* want, int nwant) {
+        uint32_t lens[2] = {0, 0};
+        for (int k = 0; k < nwant; ++k) {
+            const auto& cache = c->holes.sha1_zero;
+            const auto it = std::find_if(cache.begin(), cache.end(), [&](const auto& e) { return e.len == want[k]; });
+            if (it != cache.end()) have[n_have++] = *it;
+            else lens[n++] = want[k];
+        }
+        if (n == 0) return 0;
+        for (int k = 0; k < n; ++k) have[n_have + k].len = lens[k];
+        const int rc = ensure_holes(c, "vx_verify_files");
+        if (rc) return n = 0, rc;
+        vx_ctx::Holes& h = c->holes;
+        std::memcpy(h.h, lens, sizeof(lens));
+        hipError_t e = hipMemcpyAsync(h.d, h.h, sizeof(lens), hipMemcpyHostToDevice, h.stream);
+        if (e == hipSuccess) e = hipEventRecord(h.t0, h.stream);
+        if (e == hipSuccess)
+            e = vx::launch_sha1_zeros(reinterpret_cast<const uint32_t*>(h.d), (uint32_t)n, h.d + h.kDigestsAt, h.stream);
+        if (e == hipSuccess) e = hipEventRecord(h.t1, h.stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(h.h + h.kDigestsAt, h.d + h.kDigestsAt, (size_t)n * 20, hipMemcpyDeviceToHost, h.stream);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(h.stream);
+            return n = 0, hip_fail(e, "vx_verify_files: zero-piece digests");
+        }
+        return 0;
+    }
+    int wait() {
+        if (n == 0) return 0;
+        vx_ctx::Holes& h = c->holes;
+        const int launched = n;
+        n = 0;
+        if (hipStreamSynchronize(h.stream) != hipSuccess)
+            return fail(VX_EDEVICE, "vx_verify_files: zero-piece digests failed on the device");
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, h.t0, h.t1) == hipSuccess) h.last.zero_hash_ms = ms;
+        for (int k = 0; k < launched; ++k) {
+            vx_ctx::Holes::Sha1Zero& e = have[n_have++];
+            std::memcpy(e.digest, h.h + h.kDigestsAt + (size_t)k * 20, 20);
+            if (h.sha1_zero.size() >= h.kZeroCache) h.sha1_zero.erase(h.sha1_zero.begin());
+            h.sha1_zero.push_back(e);
+        }
+        return 0;
+    }
+};
 
 // Re-verify chunk size for `count` pieces: 256 KiB when
 // every piece's chunk fits one slot arena (a single window of rounds), else
@@ -27,11 +94,14 @@ uint64_t verify_chunk_for(const vx_ctx* c, uint64_t count) {
     return count * big <= c->slots[0].arena_cap && count <= c->slots[0].cap ? big : small;
 }
 
-// Both verify pieces [first, end) of an n-piece torrent; tags, bad[] and
-// matched_out are indexed from `first`.  Both queue reads up to kReadahead
-// slots ahead of the slot being launched (see verify_chunked).
+// Both verify the pieces `todo` (increasing; a sub-list of [first, first +
+// count): the pieces a call over file holes still has to read, DESIGN.md §6.11,
+// else all of them) of an n-piece torrent; tags, bad[] and matched_out are
+// indexed from `first`.  Slot capacities and windows count pieces to do, so a
+// sparse list does not make sparse slots or rounds.  Both queue reads up to
+// kReadahead slots ahead of the slot being launched (see verify_chunked).
 int verify_whole(FileVerify& fv, vx_files::Readers& rd, uint64_t n, uint32_t pl, uint64_t total, uint64_t first,
-                 uint64_t end) {
+                 const std::vector<uint64_t>& todo) {
     vx_ctx* c = fv.c;
     const uint64_t stride = align_up(pl, kAlign);
     const uint64_t last_len = total - (n - 1) * (uint64_t)pl;
@@ -57,7 +127,8 @@ int verify_whole(FileVerify& fv, vx_files::Readers& rd, uint64_t n, uint32_t pl,
     while (c->cfg.verify_ramp > 0 && ramp < 8 && (cap_full >> ramp) > 1 && (cap_full >> ramp) * stride > (64ull << 20))
         ++ramp;
     int filled = 0;
-    uint64_t next = first;
+    uint64_t next = 0;  // index into todo
+    const uint64_t end = todo.size();
     int rc = 0;
     while ((next < end || !q.empty()) && !rc) {
         // The slot to launch next may wait for a free slot; later ones take
@@ -78,9 +149,10 @@ int verify_whole(FileVerify& fv, vx_files::Readers& rd, uint64_t n, uint32_t pl,
             const uint64_t lo = next, hi = std::min<uint64_t>(end, next + cap);
             auto& it = items[si];
             it.clear();
-            for (uint64_t i = lo; i < hi; ++i) {
+            for (uint64_t t = lo; t < hi; ++t) {
+                const uint64_t i = todo[t];
                 const uint32_t len = (uint32_t)(i == n - 1 ? last_len : pl);
-                const uint32_t k = (uint32_t)(i - lo);
+                const uint32_t k = (uint32_t)(t - lo);
                 runs.add(it, s.h_stage + k * stride, i, len);
                 s.h_offsets[k] = k * stride;
                 s.h_lens[k] = len;
@@ -117,14 +189,15 @@ int verify_whole(FileVerify& fv, vx_files::Readers& rd, uint64_t n, uint32_t pl,
 // ramp's doubling rounds most of all).  Each round's data
 // copy is timed on the GPU (vx_tuning_last_verify).
 int verify_chunked(FileVerify& fv, vx_files::Readers& rd, uint64_t n, uint32_t pl, uint64_t total, uint64_t first,
-                   uint64_t end, uint64_t C) {
+                   uint64_t cnt, const std::vector<uint64_t>& todo, const uint8_t* hole, uint64_t C) {
     vx_ctx* c = fv.c;
     const uint64_t last_len = total - (n - 1) * (uint64_t)pl;
-    const uint64_t cnt = end - first;
+    const uint64_t end = todo.size();  // windows and rounds index todo
     ChunkPipe cp(c);
     int rc = cp.open(cnt, fv.digests_out ? nullptr : fv.expected + 20 * first, "vx_verify_files");
     if (!rc && c->verify_copy_stream) rc = cp.use_copy_stream();
-    cp.bytes = cnt * (uint64_t)pl - (end == n ? (uint64_t)pl - last_len : 0);
+    cp.hole = hole;
+    cp.bytes = end * (uint64_t)pl - (todo.back() == n - 1 ? (uint64_t)pl - last_len : 0);
     // windows of W pieces; each window runs its rounds in order
     const Slot& s0 = c->slots[0];
     const uint64_t W = std::max<uint64_t>(1, std::min<uint64_t>(s0.cap, s0.arena_cap / C));
@@ -138,15 +211,15 @@ int verify_chunked(FileVerify& fv, vx_files::Readers& rd, uint64_t n, uint32_t p
         uint64_t t_submit = 0;   // its reads queued (steady-clock ns)
     };
     std::vector<Round> rounds;
-    for (uint64_t w0 = first; w0 < end; w0 += W) {
+    for (uint64_t w0 = 0; w0 < end; w0 += W) {
         const uint64_t w1 = std::min<uint64_t>(end, w0 + W);
-        const uint64_t wmax = w1 == n ? std::max<uint64_t>(pl, last_len) : pl;
+        const uint64_t wmax = todo[w1 - 1] == n - 1 ? std::max<uint64_t>(pl, last_len) : pl;
         const int ramp = (int)c->cfg.verify_ramp;
-        const auto sched = chunk_schedule(wmax, C, w0 == first ? ramp : 0, w1 == end ? ramp : 0);
+        const auto sched = chunk_schedule(wmax, C, w0 == 0 ? ramp : 0, w1 == end ? ramp : 0);
         for (size_t k = 0; k < sched.size(); ++k) {
             const uint64_t a = sched[k].first, len = sched[k].second;
             const uint32_t fl = (k == 0 ? VX_ROUND_NEW_WINDOW : 0u) |
-                                (len < C && a < C && w0 == first ? VX_ROUND_HEAD_RAMP : 0u) |
+                                (len < C && a < C && w0 == 0 ? VX_ROUND_HEAD_RAMP : 0u) |
                                 (len < C && a >= C && w1 == end ? VX_ROUND_TAIL_RAMP : 0u);
             rounds.push_back(Round{w0, w1, a, len, k > 0, -1, 0, 0, 0, fl});
         }
@@ -170,7 +243,8 @@ int verify_chunked(FileVerify& fv, vx_files::Readers& rd, uint64_t n, uint32_t p
         auto& it = items[si];
         it.clear();
         uint32_t m = 0;
-        for (uint64_t i = r.w0; i < r.w1; ++i) {
+        for (uint64_t t = r.w0; t < r.w1; ++t) {
+            const uint64_t i = todo[t];
             const uint64_t len_i = i == n - 1 ? last_len : pl;
             if (r.a >= len_i && !(r.a == 0 && len_i == 0)) continue;  // piece already finished
             const uint64_t clen = std::min<uint64_t>(r.len, len_i - r.a);
@@ -217,6 +291,46 @@ int verify_chunked(FileVerify& fv, vx_files::Readers& rd, uint64_t n, uint32_t p
 
 namespace vxe {
 
+int ensure_holes(vx_ctx* c, const char* who) {
+    vx_ctx::Holes& h = c->holes;
+    if (h.stream) return 0;  // made together
+    hipStream_t st = nullptr;
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess)
+        return fail(VX_EDEVICE, std::string(who) + ": stream creation failed");
+    if (hipEventCreate(&h.t0) != hipSuccess || hipEventCreate(&h.t1) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void**>(&h.h), h.kZeroBlock, hipHostMallocDefault) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&h.d), h.kZeroBlock) != hipSuccess) {
+        h.stream = st;
+        free_holes(c);
+        return fail(VX_ENOMEM, std::string(who) + ": zero-hash buffers");
+    }
+    h.stream = st;
+    return 0;
+}
+
+void free_holes(vx_ctx* c) {
+    vx_ctx::Holes& h = c->holes;
+    if (h.stream) (void)hipStreamSynchronize(h.stream);
+    if (h.t0) (void)hipEventDestroy(h.t0);
+    if (h.t1) (void)hipEventDestroy(h.t1);
+    if (h.h) (void)hipHostFree(h.h);
+    if (h.d) (void)hipFree(h.d);
+    if (h.stream) (void)hipStreamDestroy(h.stream);
+    h.t0 = h.t1 = nullptr;
+    h.h = h.d = nullptr;
+    h.stream = nullptr;
+}
+
+vx_extents::Holes scan_holes(vx_ctx* c, const std::vector<int>& fds, const uint64_t* file_lengths) {
+    c->holes.last = vx_hole_trace{};
+    if (!c->holes.skip) return vx_extents::Holes();
+    const uint64_t t0 = vx_files::Readers::now_ns();
+    vx_extents::Holes holes(fds, file_lengths);
+    c->holes.last.extents = holes.extents();
+    c->holes.last.scan_ms = (vx_files::Readers::now_ns() - t0) * 1e-6;
+    return holes;
+}
+
 // vx_verify_files_range, and with sp the engine's side of a split
 // (vx_verify_files_split: pieces [sp->first, sp->end), always chunk rounds).
 int64_t verify_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
@@ -258,6 +372,38 @@ int64_t verify_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
     const int nthreads = io_threads ? (int)io_threads : (int)std::max(1u, std::min(16u, usable_cpus()));
     std::vector<uint8_t> bad(count, 0);
     if (!sp && matched_out) std::memset(matched_out, 0, count);  // (the split's pool writes its entries concurrently)
+    // Pieces that lie wholly in file holes are judged without a read (DESIGN.md
+    // §6.11): todo keeps the others.  The split and the hash call do not ask.
+    const uint64_t last_len = total - (n_pieces - 1) * (uint64_t)piece_length;
+    c->holes.last = vx_hole_trace{};
+    std::vector<uint64_t> todo;
+    std::vector<uint8_t> is_hole;  // per piece of the range; empty: none is
+    ZeroDigests zero(c);
+    if (!sp && !hashing) {
+        const vx_extents::Holes holes = scan_holes(c, fds, file_lengths);
+        if (holes.any()) {
+            vx_hole_trace& ht = c->holes.last;
+            const uint64_t t_class = vx_files::Readers::now_ns();
+            std::vector<vx_files::Seg> segs;
+            uint32_t lens[2];
+            int nlens = 0;
+            is_hole.assign(count, 0);
+            for (uint64_t i = first; i < end; ++i) {
+                if (!holes.hole_piece(fs, (int64_t)i, piece_length, segs)) continue;
+                const uint32_t len = (uint32_t)(i == n_pieces - 1 ? last_len : piece_length);
+                is_hole[i - first] = 1;
+                ht.hole_pieces++;
+                ht.hole_bytes += len;
+                if (nlens < 2 && std::find(lens, lens + nlens, len) == lens + nlens) lens[nlens++] = len;
+            }
+            ht.scan_ms += (vx_files::Readers::now_ns() - t_class) * 1e-6;
+            if (!ht.hole_pieces) is_hole.clear();
+            else if ((rc = zero.start(lens, nlens))) is_hole.clear();  // (fails the call below: nothing was read yet)
+        }
+    }
+    todo.reserve(count);
+    for (uint64_t i = first; i < end && !rc; ++i)
+        if (is_hole.empty() || !is_hole[i - first]) todo.push_back(i);
     {
         const vx_files::DirectIo dio(fds, c->cfg.direct_io != 0);
         vx_files::Readers rd(nthreads, fs, fds, piece_length, bad.data(), first, &dio);
@@ -274,17 +420,24 @@ int64_t verify_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
         c->last_verify.chunk_bytes = chunked ? Cv : 0;
         uint64_t lowest = end;
         const int regime = c->cfg.direct_io && dio.resident_fraction() < 0.5 ? 1 : 0;  // the split's learned figures
-        rc = sp        ? verify_split(fv, rd, sp, n_pieces, piece_length, total, Cv, &lowest, regime)
-             : chunked ? verify_chunked(fv, rd, n_pieces, piece_length, total, first, end, Cv)
-                       : verify_whole(fv, rd, n_pieces, piece_length, total, first, end);
+        if (rc || (!sp && todo.empty())) {
+            // the zero hashes failed to start, or every piece is a hole: no round
+        } else if (sp) {
+            rc = verify_split(fv, rd, sp, n_pieces, piece_length, total, Cv, &lowest, regime);
+        } else if (chunked) {
+            rc = verify_chunked(fv, rd, n_pieces, piece_length, total, first, count, todo,
+                                is_hole.empty() ? nullptr : is_hole.data(), Cv);
+        } else {
+            rc = verify_whole(fv, rd, n_pieces, piece_length, total, first, todo);
+        }
 
         if (!rc && !chunked) {
-            while (fv.done < count && !rc) {
+            while (fv.done < todo.size() && !rc) {
                 rc = reap(c, true);
                 fv.consume();
                 bool any = false;
                 for (auto& s : c->slots) any |= s.state == Slot::INFLIGHT;
-                if (!any && fv.done < count && !rc) rc = fail(VX_EDEVICE, "vx_verify_files: lost completions");
+                if (!any && fv.done < todo.size() && !rc) rc = fail(VX_EDEVICE, "vx_verify_files: lost completions");
             }
         }
         c->harvest_counts_mismatches = true;
@@ -300,6 +453,22 @@ int64_t verify_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
             if (matched_out) matched_out[i] = !bad[i];
             if (bad[i]) std::memset(digests_out + i * 20, 0, 20);
         }
+    }
+    // The hole pieces' verdicts: the expected row against the zero digest of
+    // the piece's length (started before the first read, waited for here; also
+    // when the call failed, so nothing of it still runs).
+    const int zrc = zero.wait();
+    if (!rc) rc = zrc;
+    for (uint64_t k = 0; k < is_hole.size() && !rc; ++k) {
+        if (!is_hole[k]) continue;
+        const uint64_t i = first + k;
+        const uint32_t len = (uint32_t)(i == n_pieces - 1 ? last_len : piece_length);
+        const uint8_t* z = zero.get(len);
+        const bool ok = z && std::memcmp(expected + 20 * i, z, 20) == 0;
+        matched_out[k] = ok ? 1 : 0;
+        c->stats.pieces_completed++;
+        c->stats.bytes_completed += len;
+        c->stats.pieces_mismatched += !ok;
     }
     return end_files_call(c, fds, bad, t_call, rc);
 }
@@ -406,6 +575,27 @@ int64_t vx_verify_files_multi(vx_ctx* const* ctxs, size_t nctx, const char* cons
         return vx_verify_files_range(ctxs[k], paths, file_lengths, nfiles, piece_length, expected, n_pieces, first,
                                      count, matched_out + first, per_ctx);
     });
+}
+
+int vx_set_skip_holes(vx_ctx* c, int on) {
+    if (!c || (on != 0 && on != 1)) return fail(VX_EINVAL, "vx_set_skip_holes: NULL context, or on not 0/1");
+    c->holes.skip = on;
+    return 0;
+}
+
+int vx_last_verify_holes(const vx_ctx* c, vx_hole_trace* out) {
+    if (!c || !out) return fail(VX_EINVAL, "vx_last_verify_holes: NULL argument");
+    *out = c->holes.last;
+    return 0;
+}
+
+int vx_sha1_device_zeros(const uint32_t* d_lens, uint32_t n, void* d_digests, void* stream) {
+    if (n == 0) return 0;
+    if (!d_lens || !d_digests) return fail(VX_EINVAL, "vx_sha1_device_zeros: NULL argument");
+    if ((reinterpret_cast<uintptr_t>(d_lens) | reinterpret_cast<uintptr_t>(d_digests)) & 3)
+        return fail(VX_EINVAL, "vx_sha1_device_zeros: d_lens and d_digests must be 4-byte aligned");
+    hipError_t e = vx::launch_sha1_zeros(d_lens, n, static_cast<uint8_t*>(d_digests), static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : hip_fail(e, "sha1 zero kernel launch");
 }
 
 int vx_last_verify(const vx_ctx* c, vx_verify_trace* out) {

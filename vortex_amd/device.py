@@ -495,6 +495,57 @@ def hybrid_pieces(data: torch.Tensor, offsets: torch.Tensor, lens: torch.Tensor,
     return sha1, roots, matched
 
 
+def _zero_lens(lens, lo: int, hi: int, device, who: str) -> torch.Tensor:
+    """The lengths of a zero-hash call as an int32 device tensor (the kernels
+    read them as uint32): a host sequence of ints, checked here, or an int32
+    device tensor, checked on the device with one copy back (a sync)."""
+    if isinstance(lens, torch.Tensor):
+        _req(lens, "lens", torch.int32)
+        if lens.numel():
+            mn, mx = torch.stack([lens.min(), lens.max()]).cpu().tolist()
+            if mn < lo or mx > hi:
+                raise ValueError(f"{who}: a length is outside {lo}..{hi}")
+        return lens.reshape(-1)
+    vals = [int(x) for x in lens]
+    if any(not lo <= x <= hi for x in vals):
+        raise ValueError(f"{who}: a length is outside {lo}..{hi}")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    return torch.tensor(vals, dtype=torch.int64).to(torch.int32).to(dev)  # (above 2^31: the same bits)
+
+
+def sha1_zeros(lens, device=None, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """SHA-1 of lens[j] zero bytes for every j, hashed from nothing
+    (vx_sha1_device_zeros): the digest an unwritten piece's expected row is
+    compared with when the re-verify skips file holes.  lens: a sequence of
+    ints (0..2^32-1), or an int32 device tensor (0..2^31-1).  Returns [n,20]
+    uint8 on the device.  Enqueue-only for a host sequence."""
+    d_lens = _zero_lens(lens, 0, (1 << 32) - 1 if not isinstance(lens, torch.Tensor) else (1 << 31) - 1, device,
+                        "sha1_zeros")
+    n, dev = d_lens.numel(), d_lens.device
+    out = torch.empty((n, 20), dtype=torch.uint8, device=dev)
+    if stream is not None:
+        d_lens.record_stream(stream)
+        out.record_stream(stream)
+    check(lib().vx_sha1_device_zeros(d_lens.data_ptr(), n, out.data_ptr(), _stream_ptr(stream, dev)),
+          "vx_sha1_device_zeros")
+    return out
+
+
+def merkle_zero_leaves(lens, device=None, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """The v2 leaf rows of unwritten blocks (vx_merkle_device_zero_leaves):
+    SHA-256 of lens[j] zero bytes, lens[j] in 1..16384, hashed from nothing.
+    lens as for sha1_zeros.  Returns [n,32] uint8 on the device."""
+    d_lens = _zero_lens(lens, 1, 16384, device, "merkle_zero_leaves")
+    n, dev = d_lens.numel(), d_lens.device
+    out = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    if stream is not None:
+        d_lens.record_stream(stream)
+        out.record_stream(stream)
+    check(lib().vx_merkle_device_zero_leaves(d_lens.data_ptr(), n, out.data_ptr(), _stream_ptr(stream, dev)),
+          "vx_merkle_device_zero_leaves")
+    return out
+
+
 SKIP_ROW = 0xFFFFFFFF  # merkle_blocks: a block that stores no leaf row
 
 

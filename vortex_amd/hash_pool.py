@@ -136,6 +136,7 @@ class HashPool:
         self._cbuf_hy = (_lib.vx_hybrid_completion * 1024)()
         self._registered: dict[int, tuple[int, Any, Any]] = {}  # id(buf) -> (address, keep-alive, buf)
         self._hybrid_rows = 0  # rows of the tables given to set_hybrid_tables
+        self._skip_holes = False  # vx_set_skip_holes' default
 
     # -- lifecycle ---------------------------------------------------------
     def close(self) -> None:
@@ -453,6 +454,28 @@ class HashPool:
         d["copy_GiBps"] = t.copy_bytes / gib / (t.copy_busy_ms * 1e-3) if t.copy_busy_ms else None
         d["copy_busy_frac"] = t.copy_busy_ms / t.copy_span_ms if t.copy_span_ms else None
         return d
+
+    @property
+    def skip_holes(self) -> bool:
+        """Whether verify_files / verify_merkle_files judge ranges the file
+        system never wrote without reading them (vx_set_skip_holes, DESIGN.md
+        §6.11).  Off by default; the split, the hybrid and the hash calls
+        ignore it."""
+        return self._skip_holes
+
+    @skip_holes.setter
+    def skip_holes(self, on: bool) -> None:
+        check(self.lib.vx_set_skip_holes(self._h, 1 if on else 0), "vx_set_skip_holes", self.lib)
+        self._skip_holes = bool(on)
+
+    def last_verify_holes(self) -> dict:
+        """What the last verify_files / verify_merkle_files call skipped
+        (vx_last_verify_holes): hole_pieces, hole_blocks, hole_bytes, the
+        extents scanned, scan_ms and zero_hash_ms.  All zero with skip_holes
+        off."""
+        t = _lib.vx_hole_trace()
+        check(self.lib.vx_last_verify_holes(self._h, ctypes.byref(t)), "vx_last_verify_holes", self.lib)
+        return {name: getattr(t, name) for name, _ in _lib.vx_hole_trace._fields_}
 
     def last_verify_rounds(self) -> list[dict]:
         """The last verify_files call's round timeline (vx_last_verify_rounds):
