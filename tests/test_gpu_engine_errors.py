@@ -15,12 +15,17 @@
 * One ownership rule for submits (vx_hash.h): a piece is taken iff the submit
   returns 0, so every piece comes back exactly once — polled, refused with
   its buffer, or unfinished after a device failure.
+* A v2 or hybrid files call (verify or hash) whose k-th block round fails
+  between its copies and its first kernel returns the error after the queued
+  part finished, and the same context's next call is exact.
 """
 import hashlib
 import mmap
+import os
 import random
 import time
 
+import numpy as np
 import pytest
 
 import oracle
@@ -397,3 +402,96 @@ def test_chunk_round_failure_then_reuse_and_destroy(built, gpu, tmp_path, copy_s
             got, bad = pool.verify_files([str(path)], [n * pl], pl, exp, io_threads=4)
             assert got == want and bad == 0
             assert pool.stats()["chunk_rounds"] > fail_at
+
+
+# ---- block rounds (v2 and hybrid files calls) ------------------------------------
+
+BLOCK_ROUND_PL = 65536
+# about 2.5 MiB in 44 pieces; slots of 256 KiB hold 16 blocks (v2) or a window of 4 pieces (hybrid): ~11 rounds
+BLOCK_ROUND_FILES = [700000, 1, 0, 65536, 65537, 16385, 900001, 300000, 524293]
+BLOCK_ROUND_DAMAGED = 19  # file 6, byte 200,000: its 4th piece, behind the 16 pieces of files 0-5
+
+
+@pytest.fixture(scope="module")
+def block_round_torrent(tmp_path_factory):
+    """The files on disk with one byte damaged, and hashlib's tables: of the
+    intact bytes (what the verify calls are given) and of the bytes on disk
+    (what the hash calls must return)."""
+    from vortex_amd import hybrid, merkle
+
+    pl, flens = BLOCK_ROUND_PL, BLOCK_ROUND_FILES
+    root = tmp_path_factory.mktemp("block_rounds")
+    rng = np.random.default_rng(0xB10C)
+    datas = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in flens]
+    on_disk = list(datas)
+    on_disk[6] = datas[6][:200000] + bytes([datas[6][200000] ^ 0x10]) + datas[6][200001:]
+    paths = []
+    for k, d in enumerate(on_disk):
+        paths.append(os.path.join(str(root), f"f{k}.bin"))
+        with open(paths[-1], "wb") as f:
+            f.write(d)
+    findex, foff, dlen, pads, lw = hybrid.hybrid_pieces(flens, pl)
+
+    def tables(files):
+        parts = [files[f][o:o + n] for f, o, n in zip(findex, foff, dlen)]
+        return ([hybrid.v1_digest(p, pad) for p, pad in zip(parts, pads)],
+                [hybrid.v2_root(p, w) for p, w in zip(parts, lw)])
+
+    sha1, rows = tables(datas)
+    disk_sha1, disk_rows = tables(on_disk)
+    n = len(rows)
+    assert n == 44 and [i for i in range(n) if rows[i] != disk_rows[i]] == [BLOCK_ROUND_DAMAGED]
+    assert [i for i in range(n) if sha1[i] != disk_sha1[i]] == [BLOCK_ROUND_DAMAGED]
+    counts, _ = merkle.tree_layout(flens, pl)
+    tree, at = b"", 0
+    for c in counts:
+        tree += merkle.build_tree(disk_rows[at:at + c], merkle.log2_width(pl)) if c else b""
+        at += c
+    return {"paths": paths, "flens": flens, "pl": pl, "n": n, "sha1": b"".join(sha1), "rows": b"".join(rows),
+            "disk_sha1": b"".join(disk_sha1), "disk_rows": b"".join(disk_rows), "disk_tree": tree}
+
+
+@pytest.mark.parametrize("kind", ["merkle_verify", "merkle_hash", "hybrid_verify_copy_stream",
+                                  "hybrid_verify_slot_streams", "hybrid_hash"])
+def test_block_round_failure_then_reuse_and_destroy(built, gpu, block_round_torrent, kind):
+    """A v2 or hybrid files call whose k-th block round fails after its copies
+    were queued (injected: vx_tuning_fail_launch_after, between the copies and
+    the first kernel; nothing faults on the device), at the first round, a
+    middle one and the last.  The call returns VX_EDEVICE with exactly k
+    rounds enqueued; the same context's next call of the same kind gives
+    hashlib's verdicts, digests, rows and trees, with the damaged piece
+    failing; the pool then closes cleanly."""
+    from vortex_amd._lib import VX_EDEVICE, VxError
+    from vortex_amd.hash_pool import HashPool
+
+    t = block_round_torrent
+    args = (t["paths"], t["flens"], t["pl"])
+    ok = [i != BLOCK_ROUND_DAMAGED for i in range(t["n"])]
+
+    def call(pool):
+        if kind == "merkle_verify":
+            return pool.verify_merkle_files(*args, t["rows"], io_threads=4)
+        if kind == "merkle_hash":
+            return pool.hash_merkle_files(*args, io_threads=4)
+        if kind == "hybrid_hash":
+            return pool.hash_hybrid_files(*args, io_threads=4)
+        return pool.verify_hybrid_files(*args, t["sha1"], t["rows"], io_threads=4)
+
+    want = {"merkle_verify": (ok, 0),
+            "merkle_hash": (t["disk_rows"], [True] * t["n"], t["disk_tree"], 0),
+            "hybrid_hash": (t["disk_sha1"], t["disk_rows"], [True] * t["n"], t["disk_tree"], 0)
+            }.get(kind, [(v, v) for v in ok])
+    rounds = None
+    for fail_at in (0, 4, None):  # None: the last round, counted by the first clean call
+        if fail_at is None:
+            fail_at = rounds - 1
+        with HashPool(t["pl"], slots=3, slot_bytes=262144, hooks=True) as pool:
+            pool.lib.vx_tuning_verify_copy_stream(pool._h, 0 if kind == "hybrid_verify_slot_streams" else 1)
+            pool.lib.vx_tuning_fail_launch_after(pool._h, fail_at)
+            with pytest.raises(VxError) as ei:
+                call(pool)
+            assert ei.value.code == VX_EDEVICE and "injected" in str(ei.value)
+            assert pool.last_verify()["rounds"] == fail_at
+            assert call(pool) == want
+            rounds = pool.last_verify()["rounds"]
+            assert rounds >= 10 and fail_at < rounds

@@ -22,16 +22,19 @@
 #include <map>
 #include <unordered_map>
 #include <numeric>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
 
+#include "vx_block_rounds.hpp"
 #include "vx_extents.hpp"
 #include "vx_files.hpp"
 #include "vx_hash.h"
 #include "vx_hybrid_slot.hpp"
 #include "vx_kernels.h"
 #include "vx_merkle_rounds.hpp"
+#include "vx_merkle_tree.hpp"
 #include "vx_synth.h"
 #include "vx_tuning.h"
 
@@ -438,6 +441,115 @@ inline int64_t end_files_call(vx_ctx* c, const std::vector<int>& fds, const std:
     c->stats.io_errors += (uint64_t)nbad;
     return nbad;
 }
+
+// ---- The frame the v2 and the hybrid files call share (vx_merkle_files.hip, vx_hybrid.hip); a call
+// keeps its buffers, what one round puts on the streams, its own stream syncs and its verdict fold. ----
+// The argument checks (null_args: the caller's own NULL test of `names`), then begin_bulk_call.
+inline int begin_block_call(vx_ctx* c, const std::string& who, bool null_args, const char* names,
+                            const uint64_t* file_lengths, size_t nfiles, uint32_t piece_length, size_t n_pieces,
+                            size_t first, size_t count, uint64_t max_count, const uint8_t* tree_out,
+                            uint64_t tree_rows) {
+    if (!c) return fail(VX_EINVAL, who + ": NULL context");
+    if (null_args) return fail(VX_EINVAL, who + ": NULL " + names);
+    if (piece_length < VX_MERKLE_BLOCK || (piece_length & (piece_length - 1)))
+        return fail(VX_EINVAL, who + ": piece_length must be a power of two >= 16384");
+    if (n_pieces != vx_merkle::torrent_pieces(file_lengths, nfiles, piece_length))
+        return fail(VX_EINVAL, who + ": n_pieces does not match the files");
+    if (first > n_pieces || count > n_pieces - first) return fail(VX_EINVAL, who + ": piece range outside the torrent");
+    if (count > max_count) return fail(VX_EINVAL, who + ": more than 2^32 pieces in one call");
+    if (tree_out && (uint64_t)vx_merkle::tree_layout(file_lengths, nfiles, piece_length, nullptr, nullptr) != tree_rows)
+        return fail(VX_EINVAL, who + ": tree_rows is not what vx_merkle_tree_layout returns");
+    return begin_bulk_call(c, who, /*need_idle=*/true);
+}
+// VX_TEST_HOOKS: a round's injected failure, between its copies and its first kernel.
+inline int injected_launch_failure(vx_ctx* c, const std::string& who) {
+#ifdef VX_TEST_HOOKS
+    if (c->fail_launch_after >= 0 && c->fail_launch_after-- == 0)
+        return fail(VX_EDEVICE, who + ": injected launch failure (vx_tuning_fail_launch_after)");
+#endif
+    return 0;
+}
+// One call, made once its buffers exist: begin(), vx_block_rounds::run (this as
+// the slots) over readers(), sync_slots(), the call's downloads, trace(), its fold, end().
+struct BlockCall {
+    vx_ctx* const c;
+    const std::string& who;
+    const size_t first, count;
+    const uint64_t t_call = vx_files::Readers::now_ns();
+    std::vector<int> fds;
+    std::vector<uint8_t> bad;  // per piece of the range: it lacks bytes
+    const std::vector<vx_files::FileSpan> no_spans;
+    std::optional<vx_files::DirectIo> dio;
+    std::optional<vx_files::Readers> rd;
+    vx_block_rounds::Totals totals;
+
+    // The traces reset; behind the caller's copies of the expected tables
+    // (tables_ok), the pieces' log2w column and the zeroed verdict bytes; then the files.
+    int begin(bool tables_ok, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
+              uint32_t piece_length, uint8_t* d_lw, uint8_t* d_verdicts, size_t verdict_bytes, uint8_t* matched_out) {
+        c->last_verify = vx_verify_trace{};
+        c->last_rounds.clear();
+        c->verify_t0_ns = t_call;
+        std::vector<uint8_t> lw(count);
+        vx_merkle::PieceCursor pc(file_lengths, nfiles, piece_length);
+        pc.seek(first);
+        for (size_t i = 0; i < count; ++i, pc.next()) lw[i] = (uint8_t)pc.log2w();
+        if (!tables_ok || hipMemcpy(d_lw, lw.data(), count, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemset(d_verdicts, 0, verdict_bytes) != hipSuccess ||
+            hipStreamSynchronize(nullptr) != hipSuccess)  // (the slot streams do not wait for the null stream)
+            return fail(VX_EDEVICE, who + ": expected-table upload failed");
+        fds.assign(nfiles, -1);
+        for (size_t f = 0; f < nfiles; ++f) fds[f] = open(paths[f], O_RDONLY | O_CLOEXEC);
+        bad.assign(count, 0);
+        if (matched_out) std::memset(matched_out, 0, count);
+        return 0;
+    }
+    // The readers of the rounds: runs of 16 KiB blocks, O_DIRECT where it pays.
+    vx_files::Readers& readers(uint32_t io_threads, uint32_t piece_length) {
+        dio.emplace(fds, c->cfg.direct_io != 0);
+        return rd.emplace(io_threads ? (int)io_threads : (int)std::max(1u, std::min(16u, usable_cpus())), no_spans, fds,
+                          piece_length, bad.data(), first, &*dio, true);
+    }
+    // The slots of vx_block_rounds::run: a slot's last round is done when its `done` event is.
+    int done(size_t si, bool block) const {
+        const Slot& s = c->slots[si];
+        const hipError_t q = block ? hipEventSynchronize(s.done) : hipEventQuery(s.done);
+        if (q == hipErrorNotReady) return vx_block_rounds::kNotYet;
+        return q == hipSuccess ? 0 : fail(VX_EDEVICE, who + ": wait failed");
+    }
+    uint8_t* stage(size_t si, int* rc) const {
+        *rc = ensure_stage(c, c->slots[si]);
+        return c->slots[si].h_stage;
+    }
+    // After the rounds, error or not: no copy or kernel may still use a stage.
+    void sync_slots(int& rc) const {
+        for (const Slot& s : c->slots)
+            if (s.stream && hipStreamSynchronize(s.stream) != hipSuccess && !rc)
+                rc = fail(VX_EDEVICE, who + ": a round failed on the device");
+    }
+    // vx_last_verify, once the results are on the host.
+    void trace(uint64_t chunk_bytes) {
+        vx_verify_trace& vt = c->last_verify;
+        vt.tail_ms = (vx_files::Readers::now_ns() - totals.last_enqueue_ns) * 1e-6;
+        trace_reads(vt, *rd, *dio, t_call);
+        vt.rounds = (uint32_t)totals.rounds;
+        vt.copy_bytes = totals.copy_bytes;
+        vt.chunk_bytes = chunk_bytes;
+    }
+    // vx_stats (mismatched: without the pieces that lack bytes, which end_files_call counts) and the result.
+    int64_t end(int rc, uint64_t mismatched) {
+        if (!rc) {
+            c->stats.pieces_completed += count;
+            c->stats.pieces_mismatched += mismatched;
+            c->stats.bytes_completed += totals.file_bytes;
+            c->stats.batches += totals.rounds;
+        }
+        rd.reset();
+        dio.reset();
+        return end_files_call(c, fds, bad, t_call, rc);
+    }
+};
+
 // Skipping file holes (vx_reverify.hip).  ensure_holes: the zero hashes'
 // stream, events and blocks.  scan_holes: the files' extents when the setting
 // is on (else an empty set, nothing scanned), counted and timed into the
@@ -445,8 +557,8 @@ inline int64_t end_files_call(vx_ctx* c, const std::vector<int>& fds, const std:
 int ensure_holes(vx_ctx* c, const char* who);
 vx_extents::Holes scan_holes(vx_ctx* c, const std::vector<int>& fds, const uint64_t* file_lengths);
 void free_holes(vx_ctx* c);
-void free_merkle_files(vx_ctx* c);  // vx_merkle.hip: vx_merkle_verify_files' buffers, not its event
-// vx_merkle.hip, the end of a v2 or hybrid hash call: the layer trees of every
+void free_merkle_files(vx_ctx* c);  // vx_merkle_files.hip: vx_merkle_verify_files' buffers, not its event
+// vx_merkle_files.hip, the end of a v2 or hybrid hash call: the layer trees of every
 // non-empty file (vx_merkle_tree_layout) from d_rows, the whole torrent's piece
 // rows on the device in piece order, into tree_out; synchronous, on st, with a
 // device block of its own.  bad[i] != 0 (piece i lacks bytes) zeroes the tree

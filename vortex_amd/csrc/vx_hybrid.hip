@@ -1,11 +1,10 @@
 // vx_hybrid.hip — the hybrid (BEP 52 "upgrade path", v1 + v2) entries of
 // vx_hash.h: vx_hybrid_device_pieces and vx_hybrid_verify_files / _range
 // (kernels in sha1_kernels.hip, sha1_tail_kernels.hip and sha256_kernels.hip;
-// the rounds in vx_hybrid_rounds.hpp), and the three tuning kernel entries.  The
-// hybrid download path (vx_hybrid_submit) is in vx_slots.hip.
+// the rounds in vx_hybrid_rounds.hpp, run by vx_block_rounds.hpp), and the three tuning
+// kernel entries.  The hybrid download path (vx_hybrid_submit) is in vx_slots.hip.
 #include "vx_chunk_pipe.hpp"
 #include "vx_hybrid_rounds.hpp"
-#include "vx_merkle_tree.hpp"
 
 using namespace vxe;
 
@@ -79,20 +78,10 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
                           uint64_t tree_rows = 0) {
     const bool hashing = sha1_out && rows_out;
     const std::string who = hashing ? "vx_hybrid_hash_files" : "vx_hybrid_verify_files";
-    if (!c) return fail(VX_EINVAL, who + ": NULL context");
-    if (!paths || !file_lengths || (!hashing && (!exp_sha1 || !exp_roots || !matched_out)))
-        return fail(VX_EINVAL, who + ": NULL paths/file_lengths/exp_sha1/exp_roots/matched_out");
-    if (piece_length < VX_MERKLE_BLOCK || (piece_length & (piece_length - 1)))
-        return fail(VX_EINVAL, who + ": piece_length must be a power of two >= 16384");
-    if (n_pieces != vx_merkle::torrent_pieces(file_lengths, nfiles, piece_length))
-        return fail(VX_EINVAL, who + ": n_pieces does not match the files");
-    if (first > n_pieces || count > n_pieces - first) return fail(VX_EINVAL, who + ": piece range outside the torrent");
-    if (count >> 32) return fail(VX_EINVAL, who + ": more than 2^32 pieces in one call");
-    if (tree_out && (uint64_t)vx_merkle::tree_layout(file_lengths, nfiles, piece_length, nullptr, nullptr) != tree_rows)
-        return fail(VX_EINVAL, who + ": tree_rows is not what vx_merkle_tree_layout returns");
-    int rc = begin_bulk_call(c, who, /*need_idle=*/true);
-    if (rc) return rc;
-    if (count == 0) return 0;
+    const bool null_args = !paths || !file_lengths || (!hashing && (!exp_sha1 || !exp_roots || !matched_out));
+    int rc = begin_block_call(c, who, null_args, "paths/file_lengths/exp_sha1/exp_roots/matched_out", file_lengths,
+                              nfiles, piece_length, n_pieces, first, count, UINT32_MAX, tree_out, tree_rows);
+    if (rc || count == 0) return rc;
     // A round is PCIe-bound when its copy outlasts its chain: at 0.76 us per
     // block and 50 GiB/s that takes ~640 lanes, so a round holds 1,024 chunks
     // where the arena allows, and 64 MiB at least.
@@ -126,27 +115,11 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
     uint8_t *d_exp1 = hb.d + o_exp1, *d_exp2 = hb.d + o_exp2, *d_v1 = hb.d + o_v1, *d_v2 = hb.d + o_v2;
     uint8_t *d_lw = hb.d + o_lw, *d_leaves = hb.d + o_leaves;
 
-    const uint64_t t_call = vx_files::Readers::now_ns();
-    c->last_verify = vx_verify_trace{};
-    c->last_rounds.clear();
-    c->verify_t0_ns = t_call;
-    {
-        std::vector<uint8_t> lw(count);
-        vx_merkle::PieceCursor pc(file_lengths, nfiles, piece_length);
-        pc.seek(first);
-        for (size_t i = 0; i < count; ++i, pc.next()) lw[i] = (uint8_t)pc.log2w();
-        if ((!hashing && (hipMemcpy(d_exp1, exp_sha1 + 20 * first, count * 20, hipMemcpyHostToDevice) != hipSuccess ||
-                          hipMemcpy(d_exp2, exp_roots + 32 * first, count * 32, hipMemcpyHostToDevice) != hipSuccess)) ||
-            hipMemcpy(d_lw, lw.data(), count, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemset(d_v1, 0, 2 * count) != hipSuccess ||
-            hipStreamSynchronize(nullptr) != hipSuccess)  // (the slot streams do not wait for the null stream)
-            return fail(VX_EDEVICE, who + ": expected-table upload failed");
-    }
-    std::vector<int> fds(nfiles, -1);
-    for (size_t f = 0; f < nfiles; ++f) fds[f] = open(paths[f], O_RDONLY | O_CLOEXEC);
-    const int nthreads = io_threads ? (int)io_threads : (int)std::max(1u, std::min(16u, usable_cpus()));
-    std::vector<uint8_t> bad(count, 0);
-    if (matched_out) std::memset(matched_out, 0, count);
+    BlockCall call{c, who, first, count};
+    const bool up = hashing ||
+                    (hipMemcpy(d_exp1, exp_sha1 + 20 * first, count * 20, hipMemcpyHostToDevice) == hipSuccess &&
+                     hipMemcpy(d_exp2, exp_roots + 32 * first, count * 32, hipMemcpyHostToDevice) == hipSuccess);
+    if ((rc = call.begin(up, paths, file_lengths, nfiles, piece_length, d_lw, d_v1, 2 * count, matched_out))) return rc;
     // hashing: the digests and rows land where the verify call keeps the expected ones
     uint8_t* const d_dig = hashing ? d_exp1 : nullptr;
     uint8_t* const d_rows = hashing ? d_exp2 : nullptr;
@@ -154,163 +127,92 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
     const uint8_t* const k_exp2 = hashing ? nullptr : d_exp2;
     uint8_t* const k_v1 = hashing ? nullptr : d_v1;
     uint8_t* const k_v2 = hashing ? nullptr : d_v2;
-    const size_t nslots = c->slots.size();
-    const size_t depth = nslots - 1;  // reads run ahead as far as the slots allow (as vx_merkle_verify_files)
-    uint64_t n_rounds = 0, n_bytes = 0, copy_bytes = 0;
+    // One round, its data already in slot si's stage.
+    auto enqueue = [&](size_t si, const vx_hybrid::Round& r) -> int {
+        Slot& s = c->slots[si];
+        // the round's tables in one copy: the uint64 columns, then the uint32 ones
+        const size_t m = r.l_len.size(), t = r.t_len.size(), e = r.rows.size();
+        uint8_t* h = hb.h_tab[si];
+        size_t at = 0;
+        auto put = [&](const void* src, size_t bytes) {
+            std::memcpy(h + at, src, bytes);
+            const size_t was = at;
+            at += bytes;
+            return was;
+        };
+        const size_t a_loff = put(r.l_off.data(), m * 8), a_lpoff = put(r.l_poff.data(), m * 8);
+        const size_t a_ltlen = put(r.l_tlen.data(), m * 8), a_toff = put(r.t_off.data(), t * 8);
+        const size_t a_llen = put(r.l_len.data(), m * 4), a_lpid = put(r.l_pid.data(), m * 4);
+        const size_t a_tlen = put(r.t_len.data(), t * 4), a_tpad = put(r.t_pad.data(), t * 4);
+        const size_t a_tpid = put(r.t_pid.data(), t * 4), a_rows = put(r.rows.data(), e * 4);
+        const size_t a_lens = put(r.lens.data(), e * 4);
+        uint8_t* d = hb.d_tab[si];
+        auto u64 = [&](size_t o) { return reinterpret_cast<const uint64_t*>(d + o); };
+        auto u32 = [&](size_t o) { return reinterpret_cast<const uint32_t*>(d + o); };
+        hipStream_t cs = pipe.cs ? pipe.cs : s.stream;
+        hipError_t err = hipMemcpyAsync(s.d_arena, s.h_stage, r.bytes, hipMemcpyHostToDevice, cs);
+        if (err == hipSuccess && pipe.cs) err = hipEventRecord(s.copied, cs);
+        if (err == hipSuccess) err = hipMemcpyAsync(d, h, at, hipMemcpyHostToDevice, s.stream);
+        if (err == hipSuccess && pipe.cs) err = hipStreamWaitEvent(s.stream, s.copied, 0);
+        if (err == hipSuccess && call.totals.rounds) err = hipStreamWaitEvent(s.stream, hb.chain, 0);
+        if (const int injected = err == hipSuccess ? injected_launch_failure(c, who) : 0) return injected;
+        if (err == hipSuccess)
+            err = vx::launch_chunk(s.d_arena, u64(a_loff), u32(a_llen), (uint32_t)m, u32(a_lpid), u64(a_lpoff),
+                                   u64(a_ltlen), d_states, d_dig, k_exp1, k_v1, s.stream);
+        if (err == hipSuccess && t) {  // the tails: after the states, beside everything else
+            err = hipEventRecord(hb.state[si], s.stream);
+            if (err == hipSuccess) err = hipStreamWaitEvent(hb.tail_stream, hb.state[si], 0);
+            if (err == hipSuccess)
+                err = vx::launch_zero_tail(s.d_arena, u64(a_toff), u32(a_tlen), u32(a_tpad), u32(a_tpid), (uint32_t)t,
+                                           piece_length, d_states, d_dig, k_exp1, k_v1, hb.tail_stream);
+            if (err == hipSuccess) err = hipEventRecord(hb.tailed[si], hb.tail_stream);
+        }
+        if (err == hipSuccess)
+            err = vx::launch_merkle_blocks(s.d_arena, u32(a_rows), u32(a_lens), (uint32_t)e, d_leaves, s.stream);
+        if (err == hipSuccess && r.end_window) {
+            const uint64_t k = r.w_first - first;
+            err = vx::launch_merkle_nodes(d_leaves, d_lw + k, r.w_n, r.w_log2, hashing ? d_rows + k * 32 : nullptr,
+                                          hashing ? nullptr : k_exp2 + k * 32, hashing ? nullptr : k_v2 + k, s.stream);
+        }
+        if (err == hipSuccess) err = hipEventRecord(hb.chain, s.stream);
+        // the slot's arena and tables are free again once its tails have read them too
+        if (err == hipSuccess && t) err = hipStreamWaitEvent(s.stream, hb.tailed[si], 0);
+        if (err == hipSuccess) err = hipEventRecord(s.done, s.stream);
+        if (err != hipSuccess) return hip_fail(err, (who + ": enqueue").c_str());
+        c->stats.chunk_rounds++;
+        return 0;
+    };
+    vx_files::Readers& rd = call.readers(io_threads, piece_length);
+    vx_hybrid::Rounds plan(file_lengths, nfiles, piece_length, n_pieces, first, count, stage, C);
+    rc = vx_block_rounds::run<vx_hybrid::Round>(plan, rd, c->slots.size(), call, enqueue, call.totals);
+    if (pipe.cs && hipStreamSynchronize(pipe.cs) != hipSuccess && !rc)  // no copy may still read a stage
+        rc = fail(VX_EDEVICE, who + ": a copy failed on the device");
+    call.sync_slots(rc);
+    if (hipStreamSynchronize(hb.tail_stream) != hipSuccess && !rc)
+        rc = fail(VX_EDEVICE, who + ": a tail kernel failed on the device");
+    std::vector<uint8_t> verdict(hashing ? 0 : 2 * count);
+    if (!rc && !hashing && hipMemcpy(verdict.data(), d_v1, 2 * count, hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(VX_EDEVICE, who + ": verdict download failed");
+    if (!rc && hashing &&
+        (hipMemcpy(sha1_out, d_dig, count * 20, hipMemcpyDeviceToHost) != hipSuccess ||
+         hipMemcpy(rows_out, d_rows, count * 32, hipMemcpyDeviceToHost) != hipSuccess))
+        rc = fail(VX_EDEVICE, who + ": digest and row download failed");
+    if (!rc && tree_out)  // (the whole torrent: first == 0, count == n_pieces)
+        rc = file_trees(c, d_rows, file_lengths, nfiles, piece_length, call.bad, tree_out, c->slots[0].stream, who);
+    call.trace(C);
     int64_t n_failed = 0;
-    using clk = std::chrono::steady_clock;
-    auto t_last_enqueue = clk::now();
-    {
-        const std::vector<vx_files::FileSpan> no_spans;
-        const vx_files::DirectIo dio(fds, c->cfg.direct_io != 0);
-        vx_files::Readers rd(nthreads, no_spans, fds, piece_length, bad.data(), first, &dio, true);
-        vx_hybrid::Rounds plan(file_lengths, nfiles, piece_length, n_pieces, first, count, stage, C);
-        std::vector<vx_hybrid::Round> round(nslots);
-        std::vector<std::vector<vx_files::ReadItem>> items(nslots);
-        std::vector<uint64_t> ticket(nslots, 0);
-        std::vector<uint8_t> live(nslots, 0);  // the slot carries an enqueued round
-        bool more = true, have_prev = false;
-        size_t nr = 0;  // next round to read
-        for (size_t ne = 0; !rc; ++ne) {
-            while (more && nr <= ne + depth && !rc) {
-                const size_t si = nr % nslots;
-                Slot& s = c->slots[si];
-                if (live[si]) {  // the round this slot carried: its stage and tables are free again after it
-                    const hipError_t q = nr == ne ? hipEventSynchronize(s.done) : hipEventQuery(s.done);
-                    if (q == hipErrorNotReady) break;  // read-ahead takes only a slot that is free now
-                    if (q != hipSuccess) {
-                        rc = fail(VX_EDEVICE, who + ": wait failed");
-                        break;
-                    }
-                    live[si] = 0;
-                }
-                if (!(more = plan.next(round[si]))) break;
-                if ((rc = ensure_stage(c, s))) break;
-                auto& it = items[si];
-                it.clear();
-                for (const vx_hybrid::Read& r : round[si].reads) {
-                    vx_files::ReadItem x{s.h_stage + r.stage_off, r.piece, 0, r.len};
-                    x.file = (int32_t)r.file;
-                    x.file_off = (int64_t)r.file_off;
-                    it.push_back(x);
-                }
-                ticket[si] = rd.submit(it);
-                ++nr;
-            }
-            if (rc || ne == nr) break;
-            const size_t si = ne % nslots;
-            Slot& s = c->slots[si];
-            const vx_hybrid::Round& r = round[si];
-            rd.wait(ticket[si]);
-            // the round's tables in one copy: the uint64 columns, then the uint32 ones
-            const size_t m = r.l_len.size(), t = r.t_len.size(), e = r.rows.size();
-            uint8_t* h = hb.h_tab[si];
-            size_t at = 0;
-            auto put = [&](const void* src, size_t bytes) {
-                std::memcpy(h + at, src, bytes);
-                const size_t was = at;
-                at += bytes;
-                return was;
-            };
-            const size_t a_loff = put(r.l_off.data(), m * 8), a_lpoff = put(r.l_poff.data(), m * 8);
-            const size_t a_ltlen = put(r.l_tlen.data(), m * 8), a_toff = put(r.t_off.data(), t * 8);
-            const size_t a_llen = put(r.l_len.data(), m * 4), a_lpid = put(r.l_pid.data(), m * 4);
-            const size_t a_tlen = put(r.t_len.data(), t * 4), a_tpad = put(r.t_pad.data(), t * 4);
-            const size_t a_tpid = put(r.t_pid.data(), t * 4), a_rows = put(r.rows.data(), e * 4);
-            const size_t a_lens = put(r.lens.data(), e * 4);
-            uint8_t* d = hb.d_tab[si];
-            auto u64 = [&](size_t o) { return reinterpret_cast<const uint64_t*>(d + o); };
-            auto u32 = [&](size_t o) { return reinterpret_cast<const uint32_t*>(d + o); };
-            hipStream_t cs = pipe.cs ? pipe.cs : s.stream;
-            hipError_t err = hipMemcpyAsync(s.d_arena, s.h_stage, r.bytes, hipMemcpyHostToDevice, cs);
-            if (err == hipSuccess && pipe.cs) err = hipEventRecord(s.copied, cs);
-            if (err == hipSuccess) err = hipMemcpyAsync(d, h, at, hipMemcpyHostToDevice, s.stream);
-            if (err == hipSuccess && pipe.cs) err = hipStreamWaitEvent(s.stream, s.copied, 0);
-            if (err == hipSuccess && have_prev) err = hipStreamWaitEvent(s.stream, hb.chain, 0);
-#ifdef VX_TEST_HOOKS
-            if (err == hipSuccess && c->fail_launch_after >= 0 && c->fail_launch_after-- == 0) {
-                rc = fail(VX_EDEVICE, who + ": injected launch failure (vx_tuning_fail_launch_after)");
-                break;
-            }
-#endif
-            if (err == hipSuccess)
-                err = vx::launch_chunk(s.d_arena, u64(a_loff), u32(a_llen), (uint32_t)m, u32(a_lpid), u64(a_lpoff),
-                                       u64(a_ltlen), d_states, d_dig, k_exp1, k_v1, s.stream);
-            if (err == hipSuccess && t) {  // the tails: after the states, beside everything else
-                err = hipEventRecord(hb.state[si], s.stream);
-                if (err == hipSuccess) err = hipStreamWaitEvent(hb.tail_stream, hb.state[si], 0);
-                if (err == hipSuccess)
-                    err = vx::launch_zero_tail(s.d_arena, u64(a_toff), u32(a_tlen), u32(a_tpad), u32(a_tpid),
-                                               (uint32_t)t, piece_length, d_states, d_dig, k_exp1, k_v1,
-                                               hb.tail_stream);
-                if (err == hipSuccess) err = hipEventRecord(hb.tailed[si], hb.tail_stream);
-            }
-            if (err == hipSuccess)
-                err = vx::launch_merkle_blocks(s.d_arena, u32(a_rows), u32(a_lens), (uint32_t)e, d_leaves, s.stream);
-            if (err == hipSuccess && r.end_window) {
-                const uint64_t k = r.w_first - first;
-                err = vx::launch_merkle_nodes(d_leaves, d_lw + k, r.w_n, r.w_log2, hashing ? d_rows + k * 32 : nullptr,
-                                              hashing ? nullptr : k_exp2 + k * 32, hashing ? nullptr : k_v2 + k,
-                                              s.stream);
-            }
-            if (err == hipSuccess) err = hipEventRecord(hb.chain, s.stream);
-            // the slot's arena and tables are free again once its tails have read them too
-            if (err == hipSuccess && t) err = hipStreamWaitEvent(s.stream, hb.tailed[si], 0);
-            if (err == hipSuccess) err = hipEventRecord(s.done, s.stream);
-            if (err != hipSuccess) {
-                rc = hip_fail(err, "vx_hybrid_verify_files: enqueue");
-                break;
-            }
-            have_prev = true;
-            live[si] = 1;
-            ++n_rounds;
-            c->stats.chunk_rounds++;
-            n_bytes += r.file_bytes;
-            copy_bytes += r.bytes;
-            t_last_enqueue = clk::now();
-        }
-        rd.wait();  // error path: no read may still target a stage
-        if (pipe.cs && hipStreamSynchronize(pipe.cs) != hipSuccess && !rc)  // ... and no copy may still read one
-            rc = fail(VX_EDEVICE, who + ": a copy failed on the device");
-        for (size_t si = 0; si < nslots; ++si)
-            if (c->slots[si].stream && hipStreamSynchronize(c->slots[si].stream) != hipSuccess && !rc)
-                rc = fail(VX_EDEVICE, who + ": a round failed on the device");
-        if (hipStreamSynchronize(hb.tail_stream) != hipSuccess && !rc)
-            rc = fail(VX_EDEVICE, who + ": a tail kernel failed on the device");
-        std::vector<uint8_t> verdict(hashing ? 0 : 2 * count);
-        if (!rc && !hashing && hipMemcpy(verdict.data(), d_v1, 2 * count, hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(VX_EDEVICE, who + ": verdict download failed");
-        if (!rc && hashing &&
-            (hipMemcpy(sha1_out, d_dig, count * 20, hipMemcpyDeviceToHost) != hipSuccess ||
-             hipMemcpy(rows_out, d_rows, count * 32, hipMemcpyDeviceToHost) != hipSuccess))
-            rc = fail(VX_EDEVICE, who + ": digest and row download failed");
-        if (!rc && tree_out)  // (the whole torrent: first == 0, count == n_pieces)
-            rc = file_trees(c, d_rows, file_lengths, nfiles, piece_length, bad, tree_out, c->slots[0].stream, who);
-        vx_verify_trace& vt = c->last_verify;
-        vt.tail_ms = std::chrono::duration<double, std::milli>(clk::now() - t_last_enqueue).count();
-        trace_reads(vt, rd, dio, t_call);
-        vt.rounds = (uint32_t)n_rounds;
-        vt.copy_bytes = copy_bytes;
-        vt.chunk_bytes = C;
-        if (!rc) {
-            uint64_t mism = 0;
-            for (size_t i = 0; i < count && hashing; ++i) {  // never a digest or row over bytes that were not read
-                if (matched_out) matched_out[i] = !bad[i];
-                if (bad[i]) std::memset(sha1_out + i * 20, 0, 20), std::memset(rows_out + i * 32, 0, 32);
-            }
-            for (size_t i = 0; i < count && !hashing; ++i) {
-                const uint8_t v = bad[i] ? 0 : (uint8_t)((verdict[i] ? 1 : 0) | (verdict[count + i] ? 2 : 0));
-                matched_out[i] = v;
-                n_failed += v != 3;
-                mism += v != 3 && !bad[i];  // I/O errors count in io_errors only
-            }
-            c->stats.pieces_completed += count;
-            c->stats.pieces_mismatched += mism;
-            c->stats.bytes_completed += n_bytes;
-            c->stats.batches += n_rounds;
-        }
+    uint64_t mism = 0;
+    for (size_t i = 0; i < count && hashing && !rc; ++i) {  // never a digest or row over bytes that were not read
+        if (matched_out) matched_out[i] = !call.bad[i];
+        if (call.bad[i]) std::memset(sha1_out + i * 20, 0, 20), std::memset(rows_out + i * 32, 0, 32);
     }
-    const int64_t ended = end_files_call(c, fds, bad, t_call, rc);
+    for (size_t i = 0; i < count && !hashing && !rc; ++i) {
+        const uint8_t v = call.bad[i] ? 0 : (uint8_t)((verdict[i] ? 1 : 0) | (verdict[count + i] ? 2 : 0));
+        matched_out[i] = v;
+        n_failed += v != 3;
+        mism += v != 3 && !call.bad[i];  // I/O errors count in io_errors only
+    }
+    const int64_t ended = call.end(rc, mism);
     return ended < 0 || hashing ? ended : n_failed;
 }
 

@@ -76,6 +76,7 @@ struct Read {
     uint64_t file_off, len, stage_off;
     uint64_t piece;  // the piece of its first byte
 };
+inline uint64_t stage_offset(const Read& r) { return r.stage_off; }  // (vx_block_rounds.hpp)
 
 struct Round {
     std::vector<Read> reads;

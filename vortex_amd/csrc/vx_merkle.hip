@@ -1,69 +1,12 @@
 // vx_merkle.hip — the BitTorrent v2 merkle entries of vx_hash.h (kernels in
-// sha256_kernels.hip): vx_merkle_device_*, _verify_batch, _verify_files,
-// _layers_plan, _verify_layers, _verify_proofs; the block checks
-// (_bitmap_words, _device_block_check, _check_blocks); the layer trees
-// (_tree_plan, _device_trees, _build_trees, _tree_proof, _tree_layout) and
-// _hash_files.
+// sha256_kernels.hip): vx_merkle_device_*, _verify_batch, _layers_plan,
+// _verify_layers, _verify_proofs; the block checks (_bitmap_words,
+// _device_block_check, _check_blocks) and the layer trees (_tree_plan,
+// _device_trees, _build_trees, _tree_proof, _tree_layout).  The files calls
+// (_verify_files, _hash_files) are in vx_merkle_files.hip.
 #include "vx_engine_internal.hpp"
-#include "vx_merkle_layers.hpp"
-#include "vx_merkle_tree.hpp"
 
 using namespace vxe;
-
-// The buffers of vx_merkle_verify_files (not its event).
-void vxe::free_merkle_files(vx_ctx* c) {
-    vx_ctx::MerkleFiles& m = c->mfiles;
-    if (m.d_window) (void)hipFree(m.d_window);
-    if (m.d_call) (void)hipFree(m.d_call);
-    for (uint32_t* p : m.h_tab)
-        if (p) (void)hipHostFree(p);
-    for (uint32_t* p : m.d_tab)
-        if (p) (void)hipFree(p);
-    hipEvent_t chain = m.chain;
-    m = vx_ctx::MerkleFiles{};
-    m.chain = chain;
-}
-
-int vxe::file_trees(vx_ctx* c, const uint8_t* d_rows, const uint64_t* file_lengths, size_t nfiles,
-                    uint32_t piece_length, const std::vector<uint8_t>& bad, uint8_t* tree_out, hipStream_t st,
-                    const std::string& who) {
-    if (int rc = set_device(c)) return rc;
-    std::vector<uint32_t> counts;  // of the non-empty files: their pieces are d_rows, back to back
-    for (size_t f = 0; f < nfiles; ++f)
-        if (file_lengths[f]) counts.push_back((uint32_t)((file_lengths[f] + piece_length - 1) / piece_length));
-    if (counts.empty()) return 0;
-    struct vx_merkle_tree_plan plan;
-    if (vx_merkle::plan_trees(counts.data(), (uint32_t)counts.size(), &plan, nullptr, 0, nullptr))
-        return fail(VX_EINVAL, who + ": the files' trees hold 2^32 rows or more");
-    std::vector<vx_merkle_tree_tile> tiles(plan.n_tiles);
-    std::vector<uint64_t> off(counts.size() + 1);
-    (void)vx_merkle::plan_trees(counts.data(), (uint32_t)counts.size(), &plan, tiles.data(), tiles.size(), off.data());
-    uint32_t height = 0;
-    while (((uint32_t)VX_MERKLE_BLOCK << height) < piece_length) ++height;
-    uint8_t* d = nullptr;
-    if (hipMalloc(&d, plan.tree_rows * 32 + tiles.size() * sizeof(vx_merkle_tree_tile)) != hipSuccess)
-        return fail(VX_ENOMEM, who + ": tree buffer allocation failed");
-    uint8_t* d_tiles = d + plan.tree_rows * 32;
-    int rc = 0;
-    if (hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(vx_merkle_tree_tile), hipMemcpyHostToDevice, st) !=
-        hipSuccess)
-        rc = fail(VX_EDEVICE, who + ": tile upload failed");
-    if (!rc)
-        rc = vx_merkle_device_trees(d_rows, &plan, reinterpret_cast<const vx_merkle_tree_tile*>(d_tiles), height, d, st);
-    if (!rc && hipMemcpyAsync(tree_out, d, plan.tree_rows * 32, hipMemcpyDeviceToHost, st) != hipSuccess)
-        rc = fail(VX_EDEVICE, who + ": tree download failed");
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(VX_EDEVICE, who + ": the tree passes failed");
-    (void)hipFree(d);
-    if (rc) return rc;
-    uint64_t piece = 0;
-    for (size_t k = 0; k < counts.size(); ++k) {  // never a tree over bytes that were not read
-        bool any = false;
-        for (uint32_t j = 0; j < counts[k]; ++j) any |= bad[piece + j] != 0;
-        if (any) std::memset(tree_out + off[k] * 32, 0, (off[k + 1] - off[k]) * 32);
-        piece += counts[k];
-    }
-    return 0;
-}
 
 extern "C" {
 
@@ -433,280 +376,6 @@ int vx_merkle_device_zero_leaves(const uint32_t* d_lens, uint32_t n, void* d_lea
                                                  static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail(e, "merkle zero leaf kernel launch");
     return 0;
-}
-
-// ---- vx_merkle_verify_files: the v2 re-verify from disk ----
-// Rounds of 16 KiB blocks packed by vx_merkle::Rounds, one slot's pinned stage
-// each.  Per round, on the slot's stream: the data H2D, the rows | lens table
-// in one H2D, the block kernel, and the node kernels of the groups of pieces
-// the round finished, with verdicts into the call's device rows; the kernels
-// wait for the previous round's (one event), the copies do not.  Reads run up
-// to kReadahead rounds ahead of the round being enqueued.
-
-constexpr uint64_t kMerkleRoundCap = 64ull << 20;  // a round's stage bytes at most
-constexpr uint32_t kMerkleRunBlocks = 128;         // one pread: 2 MiB at most (32 reads for 16 readers per full round)
-
-static int ensure_merkle_files(vx_ctx* c, uint64_t window_rows, uint64_t entries, uint64_t count) {
-    vx_ctx::MerkleFiles& m = c->mfiles;
-    const char* oom = "vx_merkle_verify_files: buffer allocation failed";
-    if (!m.chain && hipEventCreateWithFlags(&m.chain, hipEventDisableTiming) != hipSuccess)
-        return fail(VX_EDEVICE, "vx_merkle_verify_files: event creation failed");
-    if (m.window_rows < window_rows) {
-        if (m.d_window) (void)hipFree(m.d_window);
-        m.d_window = nullptr;
-        m.window_rows = 0;
-        if (hipMalloc(&m.d_window, window_rows * 32) != hipSuccess) return fail(VX_ENOMEM, oom);
-        m.window_rows = window_rows;
-    }
-    if (m.tab_entries < entries || m.h_tab.size() != c->slots.size()) {
-        for (uint32_t* p : m.h_tab)
-            if (p) (void)hipHostFree(p);
-        for (uint32_t* p : m.d_tab)
-            if (p) (void)hipFree(p);
-        m.h_tab.assign(c->slots.size(), nullptr);
-        m.d_tab.assign(c->slots.size(), nullptr);
-        m.tab_entries = 0;
-        for (size_t k = 0; k < c->slots.size(); ++k)
-            if (hipHostMalloc(&m.h_tab[k], entries * 8, hipHostMallocDefault) != hipSuccess ||
-                hipMalloc(&m.d_tab[k], entries * 8) != hipSuccess)
-                return fail(VX_ENOMEM, oom);
-        m.tab_entries = entries;
-    }
-    if (m.call_cap < count) {
-        if (m.d_call) (void)hipFree(m.d_call);
-        m.d_call = nullptr;
-        m.call_cap = 0;
-        const uint64_t cap = std::max<uint64_t>(count, 4096);
-        if (hipMalloc(&m.d_call, cap * 34) != hipSuccess) return fail(VX_ENOMEM, oom);
-        m.call_cap = cap;
-    }
-    return 0;
-}
-
-// The leaf row of a full unwritten block, made once per
-// context by the zero-leaf kernel itself with n = 1 (there is no host SHA-256)
-// and passed to every later launch by value.
-static int zero_leaf_row(vx_ctx* c) {
-    vx_ctx::Holes& h = c->holes;
-    if (h.have_zero_leaf) return 0;
-    int rc = ensure_holes(c, "vx_merkle_verify_files");
-    if (rc) return rc;
-    const uint32_t len = VX_MERKLE_BLOCK;
-    std::memcpy(h.h, &len, sizeof(len));
-    hipError_t e = hipMemcpyAsync(h.d, h.h, sizeof(len), hipMemcpyHostToDevice, h.stream);
-    if (e == hipSuccess) e = hipEventRecord(h.t0, h.stream);
-    if (e == hipSuccess)
-        e = vx::launch_merkle_zero_leaves(nullptr, reinterpret_cast<const uint32_t*>(h.d), 1, h.d + h.kLeafAt, nullptr,
-                                          h.stream);
-    if (e == hipSuccess) e = hipEventRecord(h.t1, h.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h.h + h.kLeafAt, h.d + h.kLeafAt, 32, hipMemcpyDeviceToHost, h.stream);
-    const hipError_t sync = hipStreamSynchronize(h.stream);
-    if (e != hipSuccess || sync != hipSuccess)
-        return hip_fail(e != hipSuccess ? e : sync, "vx_merkle_verify_files: zero leaf row");
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, h.t0, h.t1) == hipSuccess) h.last.zero_hash_ms = ms;
-    std::memcpy(h.zero_leaf, h.h + h.kLeafAt, 32);
-    h.have_zero_leaf = true;
-    return 0;
-}
-
-// rows_out set: the hash call (vx_merkle_hash_files).  No expected table; the
-// node kernels write the pieces' rows where the verify call keeps the expected
-// ones, matched_out is the call's ok_out (may be NULL), and with tree_out the
-// files' trees are built from those rows after the last round.
-static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
-                                 uint32_t piece_length, const uint8_t* expected, size_t n_pieces, size_t first,
-                                 size_t count, uint8_t* matched_out, uint32_t io_threads, uint8_t* rows_out = nullptr,
-                                 uint8_t* tree_out = nullptr, uint64_t tree_rows = 0) {
-    const bool hashing = rows_out != nullptr;
-    const char* who = hashing ? "vx_merkle_hash_files" : "vx_merkle_verify_files";
-    if (!c) return fail(VX_EINVAL, std::string(who) + ": NULL context");
-    if (hashing ? (nfiles && (!paths || !file_lengths))
-                : ((nfiles && (!paths || !file_lengths)) || (n_pieces && !expected) || (count && !matched_out)))
-        return fail(VX_EINVAL, std::string(who) + ": NULL paths/file_lengths/expected/matched_out");
-    if (piece_length < VX_MERKLE_BLOCK || (piece_length & (piece_length - 1)))
-        return fail(VX_EINVAL, std::string(who) + ": piece_length must be a power of two >= 16384");
-    if (n_pieces != vx_merkle::torrent_pieces(file_lengths, nfiles, piece_length))
-        return fail(VX_EINVAL, std::string(who) + ": n_pieces does not match the files");
-    if (first > n_pieces || count > n_pieces - first)
-        return fail(VX_EINVAL, std::string(who) + ": piece range outside the torrent");
-    if (tree_out && (uint64_t)vx_merkle::tree_layout(file_lengths, nfiles, piece_length, nullptr, nullptr) != tree_rows)
-        return fail(VX_EINVAL, std::string(who) + ": tree_rows is not what vx_merkle_tree_layout returns");
-    int rc = begin_bulk_call(c, who, /*need_idle=*/true);
-    if (rc) return rc;
-    if (count == 0) return 0;
-    const uint64_t bpr64 = std::min<uint64_t>(c->slots[0].arena_cap, kMerkleRoundCap) / VX_MERKLE_BLOCK;
-    if (bpr64 == 0) return fail(VX_ERANGE, std::string(who) + ": a slot holds no 16 KiB block");
-    const uint32_t bpr = (uint32_t)bpr64;
-    rc = set_device(c);
-    if (rc) return rc;
-    const uint32_t R =vx_merkle::Rounds::window_for(bpr, piece_length);
-    const uint32_t entries = 2 * bpr + piece_length / VX_MERKLE_BLOCK;
-    if ((rc = ensure_merkle_files(c, R, entries, count))) return rc;
-    vx_ctx::MerkleFiles& mf = c->mfiles;
-    uint8_t* d_exp = mf.d_call;
-    uint8_t* d_match = mf.d_call + mf.call_cap * 32;
-    uint8_t* d_lw = mf.d_call + mf.call_cap * 33;
-
-    const uint64_t t_call = vx_files::Readers::now_ns();
-    c->last_verify = vx_verify_trace{};
-    c->last_rounds.clear();
-    c->verify_t0_ns = t_call;
-    {
-        std::vector<uint8_t> lw(count);
-        vx_merkle::PieceCursor pc(file_lengths, nfiles, piece_length);
-        pc.seek(first);
-        for (size_t i = 0; i < count; ++i, pc.next()) lw[i] = (uint8_t)pc.log2w();
-        if ((!hashing && hipMemcpy(d_exp, expected + 32 * first, count * 32, hipMemcpyHostToDevice) != hipSuccess) ||
-            hipMemcpy(d_lw, lw.data(), count, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemset(d_match, 0, count) != hipSuccess ||
-            hipStreamSynchronize(nullptr) != hipSuccess)  // (the slot streams do not wait for the null stream)
-            return fail(VX_EDEVICE, std::string(who) + ": expected-table upload failed");
-    }
-    std::vector<int> fds(nfiles, -1);
-    for (size_t f = 0; f < nfiles; ++f) fds[f] = open(paths[f], O_RDONLY | O_CLOEXEC);
-    const int nthreads = io_threads ? (int)io_threads : (int)std::max(1u, std::min(16u, usable_cpus()));
-    std::vector<uint8_t> bad(count, 0);
-    if (matched_out) std::memset(matched_out, 0, count);
-    // Blocks that lie wholly in file holes are not read: the
-    // packer leaves them out of the stage and a kernel of their own writes
-    // their leaf rows.  The hash call does not ask.
-    c->holes.last = vx_hole_trace{};
-    const vx_extents::Holes holes = hashing ? vx_extents::Holes() : scan_holes(c, fds, file_lengths);
-    vx_merkle::HolePredicate in_hole;
-    if (holes.any()) {
-        in_hole = [&holes](uint32_t f, uint64_t off, uint32_t len) { return holes.hole(f, (int64_t)off, len); };
-        if ((rc = zero_leaf_row(c))) return end_files_call(c, fds, bad, t_call, rc);
-    }
-    const size_t nslots = c->slots.size();
-    // Reads run ahead as far as the slots allow: a v2 round carries no state,
-    // so a slot is free again as soon as its own round's kernels are done, and
-    // only the round about to be enqueued ever waits for one.
-    const size_t depth = nslots - 1;
-    uint64_t n_rounds = 0, n_bytes = 0, copy_bytes = 0;
-    using clk = std::chrono::steady_clock;
-    auto t_last_enqueue = clk::now();
-    {
-        const std::vector<vx_files::FileSpan> no_spans;
-        const vx_files::DirectIo dio(fds, c->cfg.direct_io != 0);
-        vx_files::Readers rd(nthreads, no_spans, fds, piece_length, bad.data(), first, &dio, true);
-        vx_merkle::Rounds pack(file_lengths, nfiles, piece_length, first, count, bpr, R, entries, kMerkleRunBlocks,
-                               in_hole);
-        std::vector<vx_merkle::Round> round(nslots);
-        std::vector<std::vector<vx_files::ReadItem>> items(nslots);
-        std::vector<uint64_t> ticket(nslots, 0);
-        std::vector<uint8_t> live(nslots, 0);  // the slot carries an enqueued round
-        bool more = true, have_prev = false;
-        size_t nr = 0;  // next round to read
-        for (size_t ne = 0; !rc; ++ne) {
-            while (more && nr <= ne + depth && !rc) {
-                const size_t si = nr % nslots;
-                Slot& s = c->slots[si];
-                if (live[si]) {  // the round this slot carried: its stage and tables are free again after it
-                    const hipError_t q = nr == ne ? hipEventSynchronize(s.done) : hipEventQuery(s.done);
-                    if (q == hipErrorNotReady) break;  // read-ahead takes only a slot that is free now
-                    if (q != hipSuccess) {
-                        rc = fail(VX_EDEVICE, std::string(who) + ": wait failed");
-                        break;
-                    }
-                    live[si] = 0;
-                }
-                if (!(more = pack.next(round[si]))) break;
-                if ((rc = ensure_stage(c, s))) break;
-                auto& it = items[si];
-                it.clear();
-                for (const vx_merkle::Read& r : round[si].reads) {
-                    vx_files::ReadItem x{s.h_stage + (uint64_t)r.stage_block * VX_MERKLE_BLOCK, r.piece, 0, r.len};
-                    x.file = (int32_t)r.file;
-                    x.file_off = (int64_t)r.file_off;
-                    it.push_back(x);
-                }
-                ticket[si] = rd.submit(it);
-                ++nr;
-            }
-            if (rc || ne == nr) break;
-            const size_t si = ne % nslots;
-            Slot& s = c->slots[si];
-            const vx_merkle::Round& r = round[si];
-            rd.wait(ticket[si]);
-            // the tables: rows | lens, each the block kernel's m entries, then the hole blocks'
-            const uint32_t all = (uint32_t)r.rows.size(), m = all - r.hole_blocks;
-            uint32_t* h_tab = mf.h_tab[si];
-            uint32_t* d_tab = mf.d_tab[si];
-            std::memcpy(h_tab, r.rows.data(), (size_t)all * 4);
-            std::memcpy(h_tab + all, r.lens.data(), (size_t)all * 4);
-            hipError_t e = hipSuccess;
-            if (r.bytes) e = hipMemcpyAsync(s.d_arena, s.h_stage, r.bytes, hipMemcpyHostToDevice, s.stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_tab, h_tab, (size_t)all * 8, hipMemcpyHostToDevice, s.stream);
-            if (e == hipSuccess && have_prev) e = hipStreamWaitEvent(s.stream, mf.chain, 0);
-#ifdef VX_TEST_HOOKS
-            if (e == hipSuccess && c->fail_launch_after >= 0 && c->fail_launch_after-- == 0) {
-                rc = fail(VX_EDEVICE, std::string(who) + ": injected launch failure (vx_tuning_fail_launch_after)");
-                break;
-            }
-#endif
-            if (e == hipSuccess && m)
-                e = vx::launch_merkle_blocks(s.d_arena, d_tab, d_tab + all, m, mf.d_window, s.stream);
-            if (e == hipSuccess && r.hole_blocks)
-                e = vx::launch_merkle_zero_leaves(d_tab + m, d_tab + all + m, r.hole_blocks, mf.d_window,
-                                                  c->holes.zero_leaf, s.stream);
-            for (const vx_merkle::Nodes& g : r.nodes) {
-                if (e != hipSuccess) break;
-                const uint64_t k = g.first - first;
-                e = vx::launch_merkle_nodes(mf.d_window + (size_t)g.row0 * 32, d_lw + k, g.n, g.log2_width,
-                                            hashing ? d_exp + k * 32 : nullptr, hashing ? nullptr : d_exp + k * 32,
-                                            hashing ? nullptr : d_match + k, s.stream);
-            }
-            if (e == hipSuccess) e = hipEventRecord(mf.chain, s.stream);
-            if (e == hipSuccess) e = hipEventRecord(s.done, s.stream);
-            if (e != hipSuccess) {
-                rc = hip_fail(e, "vx_merkle_verify_files: enqueue");
-                break;
-            }
-            have_prev = true;
-            live[si] = 1;
-            ++n_rounds;
-            n_bytes += r.file_bytes;
-            copy_bytes += r.bytes;
-            c->holes.last.hole_blocks += r.hole_blocks;
-            c->holes.last.hole_bytes += r.hole_bytes;
-            t_last_enqueue = clk::now();
-        }
-        rd.wait();  // error path: no read may still target a stage
-        for (size_t si = 0; si < nslots; ++si)  // ... and no copy may still read one
-            if (c->slots[si].stream && hipStreamSynchronize(c->slots[si].stream) != hipSuccess && !rc)
-                rc = fail(VX_EDEVICE, std::string(who) + ": a round failed on the device");
-        std::vector<uint8_t> verdict(hashing ? 0 : count);
-        if (!rc && !hashing && hipMemcpy(verdict.data(), d_match, count, hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(VX_EDEVICE, std::string(who) + ": verdict download failed");
-        if (!rc && hashing && hipMemcpy(rows_out, d_exp, count * 32, hipMemcpyDeviceToHost) != hipSuccess)
-            rc = fail(VX_EDEVICE, std::string(who) + ": row download failed");
-        if (!rc && tree_out)  // (the whole torrent: first == 0, count == n_pieces)
-            rc = file_trees(c, d_exp, file_lengths, nfiles, piece_length, bad, tree_out, c->slots[0].stream, who);
-        vx_verify_trace& vt = c->last_verify;
-        vt.tail_ms = std::chrono::duration<double, std::milli>(clk::now() - t_last_enqueue).count();
-        trace_reads(vt, rd, dio, t_call);
-        vt.rounds = (uint32_t)n_rounds;
-        vt.copy_bytes = copy_bytes;
-        vt.chunk_bytes = (uint64_t)bpr * VX_MERKLE_BLOCK;
-        if (!rc) {
-            uint64_t mism = 0;
-            for (size_t i = 0; i < count; ++i) {
-                if (hashing) {  // never a row over bytes that were not read
-                    if (matched_out) matched_out[i] = !bad[i];
-                    if (bad[i]) std::memset(rows_out + i * 32, 0, 32);
-                    continue;
-                }
-                matched_out[i] = verdict[i] && !bad[i] ? 1 : 0;
-                mism += !verdict[i] && !bad[i];  // I/O errors count in io_errors only
-            }
-            c->stats.pieces_completed += count;
-            c->stats.pieces_mismatched += mism;
-            c->stats.bytes_completed += n_bytes;
-            c->stats.batches += n_rounds;
-        }
-    }
-    return end_files_call(c, fds, bad, t_call, rc);
 }
 
 // ---- `piece layers` and hash proofs in batches ----
@@ -1093,36 +762,6 @@ int64_t vx_merkle_tree_layout(const uint64_t* file_lengths, size_t nfiles, uint3
     const int64_t rows = vx_merkle::tree_layout(file_lengths, nfiles, piece_length, counts_out, tree_off_out);
     if (rows < 0) return fail(VX_EINVAL, "vx_merkle_tree_layout: a file has 2^32 pieces or more");
     return rows;
-}
-
-int64_t vx_merkle_hash_files_range(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
-                                   uint32_t piece_length, size_t n_pieces, size_t first, size_t count,
-                                   uint8_t* rows_out, uint8_t* ok_out, uint32_t io_threads) {
-    if (!rows_out) return fail(VX_EINVAL, "vx_merkle_hash_files: NULL rows_out");
-    return merkle_files_impl(c, paths, file_lengths, nfiles, piece_length, nullptr, n_pieces, first, count, ok_out,
-                             io_threads, rows_out);
-}
-
-int64_t vx_merkle_hash_files(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
-                             uint32_t piece_length, size_t n_pieces, uint8_t* rows_out, uint8_t* ok_out,
-                             uint8_t* tree_out, uint64_t tree_rows, uint32_t io_threads) {
-    if (!rows_out) return fail(VX_EINVAL, "vx_merkle_hash_files: NULL rows_out");
-    return merkle_files_impl(c, paths, file_lengths, nfiles, piece_length, nullptr, n_pieces, 0, n_pieces, ok_out,
-                             io_threads, rows_out, tree_out, tree_rows);
-}
-
-int64_t vx_merkle_verify_files_range(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
-                                     uint32_t piece_length, const uint8_t* expected, size_t n_pieces, size_t first,
-                                     size_t count, uint8_t* matched_out, uint32_t io_threads) {
-    return merkle_files_impl(c, paths, file_lengths, nfiles, piece_length, expected, n_pieces, first, count,
-                             matched_out, io_threads);
-}
-
-int64_t vx_merkle_verify_files(vx_ctx* c, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
-                               uint32_t piece_length, const uint8_t* expected, size_t n_pieces, uint8_t* matched_out,
-                               uint32_t io_threads) {
-    return merkle_files_impl(c, paths, file_lengths, nfiles, piece_length, expected, n_pieces, 0, n_pieces,
-                             matched_out, io_threads);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // vx_merkle_rounds.hpp — host-only round packer of the BitTorrent v2 re-verify
-// from disk (vx_merkle_verify_files in vx_merkle.hip).  No HIP in here: the
+// from disk (vx_merkle_verify_files in vx_merkle_files.hip).  No HIP in here: the
 // packer is tested on the CPU (tests/native/merkle_rounds_dump.cpp).
 //
 // A v2 piece's 16 KiB blocks are independent, so a round is any run of blocks:
@@ -118,6 +118,7 @@ struct Read {
     uint32_t stage_block;
     uint64_t piece;
 };
+inline uint64_t stage_offset(const Read& r) { return (uint64_t)r.stage_block * kBlock; }  // in bytes (vx_block_rounds.hpp)
 
 // One node launch: pieces [first, first + n), piece k's rows at ring row
 // row0 + (k << log2_width).
