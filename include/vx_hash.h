@@ -304,6 +304,15 @@ int64_t vx_last_verify_rounds(const vx_ctx* ctx, vx_verify_round* out, size_t ma
  *   v2  a 16 KiB block wholly in a hole is not read; its leaf row is the
  *       SHA-256 of its length in zero bytes, made on the GPU from nothing.  A
  *       piece's other blocks are read as before.
+ *   hybrid  (vx_hybrid_verify_files / _range) the unit is the chunk of the
+ *       call's rounds, 256 KiB (the piece where a piece is shorter than two
+ *       chunks): a chunk whose data bytes all lie in holes is not read.  Its
+ *       leaf rows are made as for v2; the SHA-1 chain crosses it on the GPU
+ *       without zeros existing anywhere, and a piece with no written chunk is
+ *       judged as a v1 hole piece is, over its data and implied pad.  A chunk
+ *       only partly in holes is read whole; so is the trailing run of
+ *       unwritten chunks of the torrent's last piece when that piece is
+ *       shorter than piece_length (and not wholly unwritten).
  * A byte is a hole byte iff it lies below min(st_size, the file's torrent
  * length) and in no data extent: bytes past the end of a short file are
  * missing, not holes, so such a file fails the pieces it fails with the setting
@@ -312,15 +321,17 @@ int64_t vx_last_verify_rounds(const vx_ctx* ctx, vx_verify_round* out, size_t ma
  * Verdicts, return values and vx_get_stats are those of the setting off (hole
  * pieces count as completed, by their bytes, and as mismatched when they are);
  * vx_last_verify's read_bytes counts only what was read.
- * vx_verify_files_split (the pool claims pieces the engine cannot pre-judge),
- * the hybrid calls and the three *_hash_files calls (a torrent is not created
- * from unwritten files) ignore the setting.  VX_EINVAL: NULL ctx, on not 0/1. */
+ * vx_verify_files_split (the pool claims pieces the engine cannot pre-judge)
+ * and the three *_hash_files calls (a torrent is not created from unwritten
+ * files) ignore the setting.  VX_EINVAL: NULL ctx, on not 0/1. */
 int vx_set_skip_holes(vx_ctx* ctx, int on);
-/* What the last vx_verify_files / vx_merkle_verify_files (or _range) call on
- * ctx skipped; all zero when the setting was off. */
+/* What the last vx_verify_files / vx_merkle_verify_files /
+ * vx_hybrid_verify_files (or _range) call on ctx skipped; all zero when the
+ * setting was off. */
 typedef struct vx_hole_trace {
-    uint64_t hole_pieces; /* v1: pieces judged without a read                      */
-    uint64_t hole_blocks; /* v2: 16 KiB blocks hashed from nothing                 */
+    uint64_t hole_pieces; /* v1, hybrid: pieces judged without a read              */
+    uint64_t hole_blocks; /* v2, hybrid: 16 KiB blocks hashed from nothing (hybrid:
+                             those of its hole pieces included)                    */
     uint64_t hole_bytes;  /* their bytes: not read, staged or copied               */
     uint64_t extents;     /* data extents the scan found, over all files           */
     double scan_ms;       /* the lseek scan and the classification                 */

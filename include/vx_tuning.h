@@ -65,6 +65,13 @@ int vx_tuning_zero_tail_kernel(const void* d_base, const uint64_t* d_tail_offs, 
 int vx_tuning_chunk_kernel(const void* d_base, const uint64_t* d_offsets, const uint32_t* d_lens, uint32_t n,
                            const uint32_t* d_pids, const uint64_t* d_poffs, const uint64_t* d_tlens,
                            uint32_t* d_states, void* d_digests, void* stream);
+/* The zero-run kernel on its own (DESIGN.md §3.8, §6.11;
+ * tests/test_gpu_hybrid_zero_run.py): lane j runs d_blocks[j] all-zero 64-byte
+ * blocks from d_states[5 * d_pids[j]..] (from the initial value when
+ * d_poffs[j] == 0: the row is then not read) and stores the state back to that
+ * row.  The d_pids of a launch are distinct.  Enqueue-only on `stream`. */
+int vx_tuning_zero_run_kernel(const uint32_t* d_pids, const uint32_t* d_poffs, const uint32_t* d_blocks, uint32_t n,
+                              uint32_t* d_states, void* stream);
 /* The kernel that ends a hybrid download slot on its own (DESIGN.md §3.8,
  * §6.9; tests/test_gpu_hybrid_tail_sweep.py): lane j with d_pads[j] != 0
  * finishes its piece as the zero-tail kernel does (every padded piece is

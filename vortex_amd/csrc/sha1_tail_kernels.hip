@@ -146,6 +146,46 @@ __global__ __launch_bounds__(kTailBlock) void sha1_zero_tail_kernel(
     if (live) tail_emit(s, pid, digests, expected, matched);
 }
 
+// A run of zeros in the middle of a piece's chain: a
+// chunk of a hybrid piece that the file system never wrote, in front of a chunk
+// that it did.  Lane j takes the state row of piece pids[j] (the IV when the
+// run starts the piece, poffs[j] == 0: the row is then not read), runs
+// blocks[j] zero blocks through the tail kernel's zero-block round (to the
+// wave's largest count, lanes that are done keep their state under a select)
+// and stores the state back to the same row: no final block, no digest, no
+// verdict.  Nothing is loaded but the three table words and the state; lanes
+// past n redo lane n - 1 (in bounds) and store nothing.
+__global__ __launch_bounds__(kTailBlock) void sha1_zero_run_kernel(const uint32_t* __restrict__ pids,
+                                                                   const uint32_t* __restrict__ poffs,
+                                                                   const uint32_t* __restrict__ blocks, uint32_t n,
+                                                                   uint32_t* __restrict__ states) {
+    const uint32_t j = blockIdx.x * kTailBlock + threadIdx.x;
+    const uint32_t jj = j < n ? j : n - 1;
+    const uint32_t z = blocks[jj];
+    const uint32_t z_wave = __builtin_amdgcn_readfirstlane(tail_wave_max(z));
+    uint32_t* st = states + (size_t)pids[jj] * 5;
+
+    State s = iv();
+    if (poffs[jj] != 0) s = State{st[0], st[1], st[2], st[3], st[4]};
+    for (uint32_t b = 0; b < z_wave; ++b) {
+        State t = s;
+        compress_known(t, ZeroWords{});
+        const bool mine = b < z;
+        s.h0 = mine ? t.h0 : s.h0;
+        s.h1 = mine ? t.h1 : s.h1;
+        s.h2 = mine ? t.h2 : s.h2;
+        s.h3 = mine ? t.h3 : s.h3;
+        s.h4 = mine ? t.h4 : s.h4;
+    }
+    if (j < n) {
+        st[0] = s.h0;
+        st[1] = s.h1;
+        st[2] = s.h2;
+        st[3] = s.h3;
+        st[4] = s.h4;
+    }
+}
+
 // The tables the chunked kernel and the tail kernel take for
 // vx_hybrid_device_pieces, from the caller's device-resident lens and pads:
 // a padded piece's chunk is its whole 64-byte blocks and is not final (total
@@ -292,6 +332,14 @@ hipError_t launch_zero_tail(const uint8_t* base, const uint64_t* tail_offs, cons
     const uint32_t blocks = (n + kTailBlock - 1) / kTailBlock;
     hipLaunchKernelGGL(sha1_zero_tail_kernel, dim3(blocks), dim3(kTailBlock), 0, stream, base, tail_offs, lens, pads,
                        pids, n, states, digests, expected, matched, fin);
+    return hipGetLastError();
+}
+
+hipError_t launch_zero_run(const uint32_t* pids, const uint32_t* poffs, const uint32_t* blocks, uint32_t n,
+                           uint32_t* states, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(sha1_zero_run_kernel, dim3((n + kTailBlock - 1) / kTailBlock), dim3(kTailBlock), 0, stream, pids,
+                       poffs, blocks, n, states);
     return hipGetLastError();
 }
 

@@ -482,7 +482,16 @@ struct BlockCall {
     std::optional<vx_files::DirectIo> dio;
     std::optional<vx_files::Readers> rd;
     vx_block_rounds::Totals totals;
+    ~BlockCall() {  // (a call that ended before end())
+        for (int fd : fds)
+            if (fd >= 0) close(fd);
+    }
 
+    // The files, ahead of begin() for a call that scans them first.
+    void open_files(const char* const* paths, size_t nfiles) {
+        fds.assign(nfiles, -1);
+        for (size_t f = 0; f < nfiles; ++f) fds[f] = open(paths[f], O_RDONLY | O_CLOEXEC);
+    }
     // The traces reset; behind the caller's copies of the expected tables
     // (tables_ok), the pieces' log2w column and the zeroed verdict bytes; then the files.
     int begin(bool tables_ok, const char* const* paths, const uint64_t* file_lengths, size_t nfiles,
@@ -498,8 +507,7 @@ struct BlockCall {
             hipMemset(d_verdicts, 0, verdict_bytes) != hipSuccess ||
             hipStreamSynchronize(nullptr) != hipSuccess)  // (the slot streams do not wait for the null stream)
             return fail(VX_EDEVICE, who + ": expected-table upload failed");
-        fds.assign(nfiles, -1);
-        for (size_t f = 0; f < nfiles; ++f) fds[f] = open(paths[f], O_RDONLY | O_CLOEXEC);
+        if (fds.empty()) open_files(paths, nfiles);
         bad.assign(count, 0);
         if (matched_out) std::memset(matched_out, 0, count);
         return 0;
@@ -546,7 +554,9 @@ struct BlockCall {
         }
         rd.reset();
         dio.reset();
-        return end_files_call(c, fds, bad, t_call, rc);
+        const int64_t ended = end_files_call(c, fds, bad, t_call, rc);
+        fds.clear();  // (closed)
+        return ended;
     }
 };
 
@@ -557,6 +567,74 @@ struct BlockCall {
 int ensure_holes(vx_ctx* c, const char* who);
 vx_extents::Holes scan_holes(vx_ctx* c, const std::vector<int>& fds, const uint64_t* file_lengths);
 void free_holes(vx_ctx* c);
+// vx_merkle_files.hip: the leaf row of a full unwritten block into c->holes.zero_leaf,
+// made once per context; synchronous, on the holes' stream (so before a ZeroDigests::start).
+int zero_leaf_row(vx_ctx* c, const char* who);
+
+// The SHA-1 digests of zero pieces a call over file holes compares expected
+// rows with (vx_verify_files and vx_hybrid_verify_files): at
+// most two lengths per call, the torrent's piece length and its last piece's.
+// start() launches sha1_zero_kernel for the lengths the context has not cached,
+// on the holes' own stream, so the chain (a 2 MiB piece: 32,768 blocks, ~24 ms)
+// runs beside the call's reads, copies and kernels; wait() takes the digests
+// into the cache.  No host hashing: the product has none.
+struct ZeroDigests {
+    vx_ctx* c;
+    const std::string who;
+    vx_ctx::Holes::Sha1Zero have[2] = {};  // the call's lengths: cached ones first, then [n_have, n_have + n) launched
+    int n_have = 0, n = 0;
+
+    ZeroDigests(vx_ctx* ctx, const char* caller) : c(ctx), who(caller) {}
+    const uint8_t* get(uint32_t len) const {
+        for (int k = 0; k < n_have; ++k)
+            if (have[k].len == len) return have[k].digest;
+        return nullptr;
+    }
+    int start(const uint32_t* want, int nwant) {
+        uint32_t lens[2] = {0, 0};
+        for (int k = 0; k < nwant; ++k) {
+            const auto& cache = c->holes.sha1_zero;
+            const auto it = std::find_if(cache.begin(), cache.end(), [&](const auto& e) { return e.len == want[k]; });
+            if (it != cache.end()) have[n_have++] = *it;
+            else lens[n++] = want[k];
+        }
+        if (n == 0) return 0;
+        for (int k = 0; k < n; ++k) have[n_have + k].len = lens[k];
+        const int rc = ensure_holes(c, who.c_str());
+        if (rc) return n = 0, rc;
+        vx_ctx::Holes& h = c->holes;
+        std::memcpy(h.h, lens, sizeof(lens));
+        hipError_t e = hipMemcpyAsync(h.d, h.h, sizeof(lens), hipMemcpyHostToDevice, h.stream);
+        if (e == hipSuccess) e = hipEventRecord(h.t0, h.stream);
+        if (e == hipSuccess)
+            e = vx::launch_sha1_zeros(reinterpret_cast<const uint32_t*>(h.d), (uint32_t)n, h.d + h.kDigestsAt, h.stream);
+        if (e == hipSuccess) e = hipEventRecord(h.t1, h.stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(h.h + h.kDigestsAt, h.d + h.kDigestsAt, (size_t)n * 20, hipMemcpyDeviceToHost, h.stream);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(h.stream);
+            return n = 0, hip_fail(e, (who + ": zero-piece digests").c_str());
+        }
+        return 0;
+    }
+    int wait() {
+        if (n == 0) return 0;
+        vx_ctx::Holes& h = c->holes;
+        const int launched = n;
+        n = 0;
+        if (hipStreamSynchronize(h.stream) != hipSuccess)
+            return fail(VX_EDEVICE, who + ": zero-piece digests failed on the device");
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, h.t0, h.t1) == hipSuccess) h.last.zero_hash_ms += ms;
+        for (int k = 0; k < launched; ++k) {
+            vx_ctx::Holes::Sha1Zero& e = have[n_have++];
+            std::memcpy(e.digest, h.h + h.kDigestsAt + (size_t)k * 20, 20);
+            if (h.sha1_zero.size() >= h.kZeroCache) h.sha1_zero.erase(h.sha1_zero.begin());
+            h.sha1_zero.push_back(e);
+        }
+        return 0;
+    }
+};
 void free_merkle_files(vx_ctx* c);  // vx_merkle_files.hip: vx_merkle_verify_files' buffers, not its event
 // vx_merkle_files.hip, the end of a v2 or hybrid hash call: the layer trees of every
 // non-empty file (vx_merkle_tree_layout) from d_rows, the whole torrent's piece

@@ -1,7 +1,7 @@
 // vx_hybrid.hip — the hybrid (BEP 52 "upgrade path", v1 + v2) entries of
 // vx_hash.h: vx_hybrid_device_pieces and vx_hybrid_verify_files / _range
 // (kernels in sha1_kernels.hip, sha1_tail_kernels.hip and sha256_kernels.hip;
-// the rounds in vx_hybrid_rounds.hpp, run by vx_block_rounds.hpp), and the three tuning
+// the rounds in vx_hybrid_rounds.hpp, run by vx_block_rounds.hpp), and the four tuning
 // kernel entries.  The hybrid download path (vx_hybrid_submit) is in vx_slots.hip.
 #include "vx_chunk_pipe.hpp"
 #include "vx_hybrid_rounds.hpp"
@@ -22,15 +22,21 @@ struct HybridBufs {
     // per slot, `state` after the round's SHA-1 kernel and `tailed` after its tails.
     hipStream_t tail_stream = nullptr;
     std::vector<hipEvent_t> state, tailed;
+    // The zero-run kernel of a round (file holes) runs beside
+    // that round's SHA-1 kernel on a stream of its own, made when a call first
+    // has a zero run: per slot, `tabled` after the round's tables are on the
+    // device and `zeroed` after its zero runs.
+    hipStream_t run_stream = nullptr;
+    std::vector<hipEvent_t> tabled, zeroed;
     ~HybridBufs() {
-        if (tail_stream) {
-            (void)hipStreamSynchronize(tail_stream);
-            (void)hipStreamDestroy(tail_stream);
-        }
-        for (hipEvent_t e : state)
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : tailed)
-            if (e) (void)hipEventDestroy(e);
+        for (hipStream_t st : {tail_stream, run_stream})
+            if (st) {
+                (void)hipStreamSynchronize(st);
+                (void)hipStreamDestroy(st);
+            }
+        for (const auto* v : {&state, &tailed, &tabled, &zeroed})
+            for (hipEvent_t e : *v)
+                if (e) (void)hipEventDestroy(e);
         if (d) (void)hipFree(d);
         for (uint8_t* p : h_tab)
             if (p) (void)hipHostFree(p);
@@ -64,6 +70,17 @@ struct HybridBufs {
         if (!ok) return fail(VX_EDEVICE, who + ": stream or event creation failed");
         return 0;
     }
+    int make_run_stream(const std::string& who) {
+        if (run_stream) return 0;
+        tabled.assign(state.size(), nullptr);
+        zeroed.assign(state.size(), nullptr);
+        bool ok = hipStreamCreateWithFlags(&run_stream, hipStreamNonBlocking) == hipSuccess;
+        for (size_t k = 0; k < state.size() && ok; ++k)
+            ok = hipEventCreateWithFlags(&tabled[k], hipEventDisableTiming) == hipSuccess &&
+                 hipEventCreateWithFlags(&zeroed[k], hipEventDisableTiming) == hipSuccess;
+        if (!ok) return fail(VX_EDEVICE, who + ": stream or event creation failed");
+        return 0;
+    }
 };
 
 // sha1_out and rows_out set: the hash call (vx_hybrid_hash_files).  Both
@@ -91,15 +108,35 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
     const uint64_t stage = std::min<uint64_t>(arena, std::max<uint64_t>(64ull << 20, 1024 * C));
     if ((rc = set_device(c))) return rc;
 
+    // Chunks that lie wholly in file holes are not read: the
+    // planner gives them no stage bytes, carries the SHA-1 state across them
+    // with zero-run lanes and the tail lanes, and has their leaf rows written by
+    // the zero-leaf kernel.  The files are opened now, for the scan; the hash
+    // call does not ask.
+    BlockCall call{c, who, first, count};
+    if (!hashing && c->holes.skip) call.open_files(paths, nfiles);
+    c->holes.last = vx_hole_trace{};
+    const vx_extents::Holes holes = hashing ? vx_extents::Holes() : scan_holes(c, call.fds, file_lengths);
+    vx_merkle::HolePredicate in_hole;
+    if (holes.any())
+        in_hole = [&holes](uint32_t f, uint64_t off, uint32_t len) { return holes.hole(f, (int64_t)off, len); };
     // What the rounds need at most (a dry run of the planner: no I/O): the
-    // leaf rows of the largest window and the bytes of the largest table.
+    // leaf rows of the largest window and the bytes of the largest table; and
+    // the pieces with no byte to read, which the host judges after the rounds.
     uint64_t rows = 1, tab_bytes = 16;
+    bool zero_runs = false;
+    std::vector<uint32_t> hole_pid, hole_len;
     {
-        vx_hybrid::Rounds dry(file_lengths, nfiles, piece_length, n_pieces, first, count, stage, C);
+        vx_hybrid::Rounds dry(file_lengths, nfiles, piece_length, n_pieces, first, count, stage, C,
+                              vx_hybrid::kRowBudget, vx_hybrid::kMaxRun, in_hole);
         vx_hybrid::Round r;
         while (dry.next(r)) {
             rows = std::max<uint64_t>(rows, (uint64_t)r.w_n << r.w_log2);
-            tab_bytes = std::max<uint64_t>(tab_bytes, r.l_len.size() * 32 + r.t_len.size() * 20 + r.rows.size() * 8);
+            tab_bytes = std::max<uint64_t>(tab_bytes, r.l_len.size() * 32 + r.t_len.size() * 20 + r.rows.size() * 8 +
+                                                          r.z_pid.size() * 12);
+            zero_runs |= !r.z_pid.empty();
+            hole_pid.insert(hole_pid.end(), r.hole_pid.begin(), r.hole_pid.end());
+            hole_len.insert(hole_len.end(), r.hole_len.begin(), r.hole_len.end());
         }
     }
     // per piece: state (20) | expected SHA-1 (20) | expected root (32) | v1 verdict | v2 verdict | log2w
@@ -115,11 +152,21 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
     uint8_t *d_exp1 = hb.d + o_exp1, *d_exp2 = hb.d + o_exp2, *d_v1 = hb.d + o_v1, *d_v2 = hb.d + o_v2;
     uint8_t *d_lw = hb.d + o_lw, *d_leaves = hb.d + o_leaves;
 
-    BlockCall call{c, who, first, count};
+    if (zero_runs && (rc = hb.make_run_stream(who))) return rc;
     const bool up = hashing ||
                     (hipMemcpy(d_exp1, exp_sha1 + 20 * first, count * 20, hipMemcpyHostToDevice) == hipSuccess &&
                      hipMemcpy(d_exp2, exp_roots + 32 * first, count * 32, hipMemcpyHostToDevice) == hipSuccess);
     if ((rc = call.begin(up, paths, file_lengths, nfiles, piece_length, d_lw, d_v1, 2 * count, matched_out))) return rc;
+    // The zero hashes: the full block's leaf row first (it is synchronous), then
+    // the digests of the hole pieces' lengths, beside the rounds.
+    ZeroDigests zero(c, who.c_str());
+    if (in_hole) {
+        uint32_t zlens[2];
+        int nz = 0;
+        for (uint32_t len : hole_len)
+            if (nz < 2 && std::find(zlens, zlens + nz, len) == zlens + nz) zlens[nz++] = len;
+        if ((rc = zero_leaf_row(c, who.c_str())) || (rc = zero.start(zlens, nz))) return call.end(rc, 0);
+    }
     // hashing: the digests and rows land where the verify call keeps the expected ones
     uint8_t* const d_dig = hashing ? d_exp1 : nullptr;
     uint8_t* const d_rows = hashing ? d_exp2 : nullptr;
@@ -131,7 +178,8 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
     auto enqueue = [&](size_t si, const vx_hybrid::Round& r) -> int {
         Slot& s = c->slots[si];
         // the round's tables in one copy: the uint64 columns, then the uint32 ones
-        const size_t m = r.l_len.size(), t = r.t_len.size(), e = r.rows.size();
+        const size_t m = r.l_len.size(), t = r.t_len.size(), z = r.z_pid.size();
+        const size_t e = r.rows.size() - r.hole_blocks;  // the block kernel's entries; the hole blocks' follow
         uint8_t* h = hb.h_tab[si];
         size_t at = 0;
         auto put = [&](const void* src, size_t bytes) {
@@ -144,18 +192,32 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
         const size_t a_ltlen = put(r.l_tlen.data(), m * 8), a_toff = put(r.t_off.data(), t * 8);
         const size_t a_llen = put(r.l_len.data(), m * 4), a_lpid = put(r.l_pid.data(), m * 4);
         const size_t a_tlen = put(r.t_len.data(), t * 4), a_tpad = put(r.t_pad.data(), t * 4);
-        const size_t a_tpid = put(r.t_pid.data(), t * 4), a_rows = put(r.rows.data(), e * 4);
-        const size_t a_lens = put(r.lens.data(), e * 4);
+        const size_t a_tpid = put(r.t_pid.data(), t * 4), a_rows = put(r.rows.data(), r.rows.size() * 4);
+        const size_t a_lens = put(r.lens.data(), r.lens.size() * 4), a_zpid = put(r.z_pid.data(), z * 4);
+        const size_t a_zpoff = put(r.z_poff.data(), z * 4), a_zblocks = put(r.z_blocks.data(), z * 4);
         uint8_t* d = hb.d_tab[si];
         auto u64 = [&](size_t o) { return reinterpret_cast<const uint64_t*>(d + o); };
         auto u32 = [&](size_t o) { return reinterpret_cast<const uint32_t*>(d + o); };
         hipStream_t cs = pipe.cs ? pipe.cs : s.stream;
-        hipError_t err = hipMemcpyAsync(s.d_arena, s.h_stage, r.bytes, hipMemcpyHostToDevice, cs);
+        hipError_t err = hipSuccess;
+        if (r.bytes) err = hipMemcpyAsync(s.d_arena, s.h_stage, r.bytes, hipMemcpyHostToDevice, cs);
         if (err == hipSuccess && pipe.cs) err = hipEventRecord(s.copied, cs);
         if (err == hipSuccess) err = hipMemcpyAsync(d, h, at, hipMemcpyHostToDevice, s.stream);
+        if (err == hipSuccess && z) err = hipEventRecord(hb.tabled[si], s.stream);
         if (err == hipSuccess && pipe.cs) err = hipStreamWaitEvent(s.stream, s.copied, 0);
         if (err == hipSuccess && call.totals.rounds) err = hipStreamWaitEvent(s.stream, hb.chain, 0);
         if (const int injected = err == hipSuccess ? injected_launch_failure(c, who) : 0) return injected;
+        if (err == hipSuccess && z) {
+            // The zero runs: after the tables and the previous round's kernels,
+            // beside this round's SHA-1 kernel (other state rows), which a chunk
+            // of zero blocks would otherwise follow for as long as it takes itself.
+            err = hipStreamWaitEvent(hb.run_stream, hb.tabled[si], 0);
+            if (err == hipSuccess && call.totals.rounds) err = hipStreamWaitEvent(hb.run_stream, hb.chain, 0);
+            if (err == hipSuccess)
+                err = vx::launch_zero_run(u32(a_zpid), u32(a_zpoff), u32(a_zblocks), (uint32_t)z, d_states,
+                                          hb.run_stream);
+            if (err == hipSuccess) err = hipEventRecord(hb.zeroed[si], hb.run_stream);
+        }
         if (err == hipSuccess)
             err = vx::launch_chunk(s.d_arena, u64(a_loff), u32(a_llen), (uint32_t)m, u32(a_lpid), u64(a_lpoff),
                                    u64(a_ltlen), d_states, d_dig, k_exp1, k_v1, s.stream);
@@ -167,32 +229,50 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
                                            piece_length, d_states, d_dig, k_exp1, k_v1, hb.tail_stream);
             if (err == hipSuccess) err = hipEventRecord(hb.tailed[si], hb.tail_stream);
         }
-        if (err == hipSuccess)
+        if (err == hipSuccess && e)
             err = vx::launch_merkle_blocks(s.d_arena, u32(a_rows), u32(a_lens), (uint32_t)e, d_leaves, s.stream);
+        if (err == hipSuccess && r.hole_blocks)
+            err = vx::launch_merkle_zero_leaves(u32(a_rows) + e, u32(a_lens) + e, r.hole_blocks, d_leaves,
+                                                c->holes.zero_leaf, s.stream);
         if (err == hipSuccess && r.end_window) {
             const uint64_t k = r.w_first - first;
             err = vx::launch_merkle_nodes(d_leaves, d_lw + k, r.w_n, r.w_log2, hashing ? d_rows + k * 32 : nullptr,
                                           hashing ? nullptr : k_exp2 + k * 32, hashing ? nullptr : k_v2 + k, s.stream);
         }
+        if (err == hipSuccess && z) err = hipStreamWaitEvent(s.stream, hb.zeroed[si], 0);
         if (err == hipSuccess) err = hipEventRecord(hb.chain, s.stream);
         // the slot's arena and tables are free again once its tails have read them too
         if (err == hipSuccess && t) err = hipStreamWaitEvent(s.stream, hb.tailed[si], 0);
         if (err == hipSuccess) err = hipEventRecord(s.done, s.stream);
         if (err != hipSuccess) return hip_fail(err, (who + ": enqueue").c_str());
         c->stats.chunk_rounds++;
+        c->holes.last.hole_pieces += r.hole_pid.size();
+        c->holes.last.hole_blocks += r.hole_blocks;
+        c->holes.last.hole_bytes += r.hole_bytes;
         return 0;
     };
     vx_files::Readers& rd = call.readers(io_threads, piece_length);
-    vx_hybrid::Rounds plan(file_lengths, nfiles, piece_length, n_pieces, first, count, stage, C);
+    vx_hybrid::Rounds plan(file_lengths, nfiles, piece_length, n_pieces, first, count, stage, C, vx_hybrid::kRowBudget,
+                           vx_hybrid::kMaxRun, in_hole);
     rc = vx_block_rounds::run<vx_hybrid::Round>(plan, rd, c->slots.size(), call, enqueue, call.totals);
     if (pipe.cs && hipStreamSynchronize(pipe.cs) != hipSuccess && !rc)  // no copy may still read a stage
         rc = fail(VX_EDEVICE, who + ": a copy failed on the device");
     call.sync_slots(rc);
     if (hipStreamSynchronize(hb.tail_stream) != hipSuccess && !rc)
         rc = fail(VX_EDEVICE, who + ": a tail kernel failed on the device");
+    if (hb.run_stream && hipStreamSynchronize(hb.run_stream) != hipSuccess && !rc)
+        rc = fail(VX_EDEVICE, who + ": a zero-run kernel failed on the device");
+    // (also when the call failed, so nothing of it still runs)
+    if (const int zrc = zero.wait(); zrc && !rc) rc = zrc;
     std::vector<uint8_t> verdict(hashing ? 0 : 2 * count);
     if (!rc && !hashing && hipMemcpy(verdict.data(), d_v1, 2 * count, hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail(VX_EDEVICE, who + ": verdict download failed");
+    // The pieces with no byte read: their v1 verdict is the expected row against
+    // the zero digest of the piece's whole length; their root came from the node kernels.
+    for (size_t k = 0; k < hole_pid.size() && !rc; ++k) {
+        const uint8_t* zd = zero.get(hole_len[k]);
+        verdict[hole_pid[k]] = zd && std::memcmp(exp_sha1 + 20 * (first + hole_pid[k]), zd, 20) == 0;
+    }
     if (!rc && hashing &&
         (hipMemcpy(sha1_out, d_dig, count * 20, hipMemcpyDeviceToHost) != hipSuccess ||
          hipMemcpy(rows_out, d_rows, count * 32, hipMemcpyDeviceToHost) != hipSuccess))
@@ -284,6 +364,14 @@ int vx_tuning_zero_tail_kernel(const void* d_base, const uint64_t* d_tail_offs, 
                                         piece_length, d_states, static_cast<uint8_t*>(d_digests), nullptr, nullptr,
                                         static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : hip_fail(e, "vx_tuning_zero_tail_kernel");
+}
+
+int vx_tuning_zero_run_kernel(const uint32_t* d_pids, const uint32_t* d_poffs, const uint32_t* d_blocks, uint32_t n,
+                              uint32_t* d_states, void* stream) {
+    if (n && (!d_pids || !d_poffs || !d_blocks || !d_states))
+        return fail(VX_EINVAL, "vx_tuning_zero_run_kernel: NULL argument");
+    hipError_t e = vx::launch_zero_run(d_pids, d_poffs, d_blocks, n, d_states, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : hip_fail(e, "vx_tuning_zero_run_kernel");
 }
 
 int vx_tuning_chunk_kernel(const void* d_base, const uint64_t* d_offsets, const uint32_t* d_lens, uint32_t n,

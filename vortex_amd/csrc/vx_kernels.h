@@ -87,6 +87,12 @@ hipError_t launch_zero_tail(const uint8_t* base, const uint64_t* tail_offs, cons
                             const uint32_t* pads, const uint32_t* pids, uint32_t n, uint64_t piece_length,
                             const uint32_t* states, uint8_t* digests, const uint8_t* expected, uint8_t* matched,
                             hipStream_t stream);
+// A run of zeros inside a piece's chain (sha1_zero_run_kernel):
+// lane j runs blocks[j] all-zero blocks from states[pids[j]*5..] (the IV when
+// poffs[j] == 0, the row is then not read) and stores the state back to that
+// row; no digest.  The pids of one launch are distinct.
+hipError_t launch_zero_run(const uint32_t* pids, const uint32_t* poffs, const uint32_t* blocks, uint32_t n,
+                           uint32_t* states, hipStream_t stream);
 // vx_hybrid_device_pieces: launch_chunk's and launch_zero_tail's tables from
 // device-resident offsets / lens / pads, and the two verdicts into one byte
 // (bit 0 = v1, bit 1 = v2; either may be NULL).

@@ -111,11 +111,11 @@ static int ensure_merkle_files(vx_ctx* c, uint64_t window_rows, uint64_t entries
 
 // The leaf row of a full unwritten block, made once per
 // context by the zero-leaf kernel itself with n = 1 (there is no host SHA-256)
-// and passed to every later launch by value.
-static int zero_leaf_row(vx_ctx* c) {
+// and passed to every later launch by value (the hybrid files call shares it).
+int vxe::zero_leaf_row(vx_ctx* c, const char* who) {
     vx_ctx::Holes& h = c->holes;
     if (h.have_zero_leaf) return 0;
-    int rc = ensure_holes(c, "vx_merkle_verify_files");
+    int rc = ensure_holes(c, who);
     if (rc) return rc;
     const uint32_t len = VX_MERKLE_BLOCK;
     std::memcpy(h.h, &len, sizeof(len));
@@ -128,9 +128,9 @@ static int zero_leaf_row(vx_ctx* c) {
     if (e == hipSuccess) e = hipMemcpyAsync(h.h + h.kLeafAt, h.d + h.kLeafAt, 32, hipMemcpyDeviceToHost, h.stream);
     const hipError_t sync = hipStreamSynchronize(h.stream);
     if (e != hipSuccess || sync != hipSuccess)
-        return hip_fail(e != hipSuccess ? e : sync, "vx_merkle_verify_files: zero leaf row");
+        return hip_fail(e != hipSuccess ? e : sync, (std::string(who) + ": zero leaf row").c_str());
     float ms = 0;
-    if (hipEventElapsedTime(&ms, h.t0, h.t1) == hipSuccess) h.last.zero_hash_ms = ms;
+    if (hipEventElapsedTime(&ms, h.t0, h.t1) == hipSuccess) h.last.zero_hash_ms += ms;
     std::memcpy(h.zero_leaf, h.h + h.kLeafAt, 32);
     h.have_zero_leaf = true;
     return 0;
@@ -172,7 +172,7 @@ static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint
     vx_merkle::HolePredicate in_hole;
     if (holes.any()) {
         in_hole = [&holes](uint32_t f, uint64_t off, uint32_t len) { return holes.hole(f, (int64_t)off, len); };
-        if ((rc = zero_leaf_row(c))) return call.end(rc, 0);
+        if ((rc = zero_leaf_row(c, who.c_str()))) return call.end(rc, 0);
     }
     // One round on slot si's stream, its data already in the stage.
     auto enqueue = [&](size_t si, const vx_merkle::Round& r) -> int {

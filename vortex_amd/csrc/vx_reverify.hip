@@ -18,70 +18,6 @@ using namespace vxe;
 
 namespace {
 
-// The SHA-1 digests of zero pieces a call over file holes compares expected
-// rows with: at most two lengths per call, the torrent's
-// piece length and its last piece's.  start() launches sha1_zero_kernel for the
-// lengths the context has not cached, on the holes' own stream, so the chain (a
-// 2 MiB piece: 32,768 blocks, ~24 ms) runs beside the call's reads, copies and
-// kernels; wait() takes the digests into the cache.  No host hashing: the
-// product has none.
-struct ZeroDigests {
-    vx_ctx* c;
-    vx_ctx::Holes::Sha1Zero have[2] = {};  // the call's lengths: cached ones first, then [n_have, n_have + n) launched
-    int n_have = 0, n = 0;
-
-    explicit ZeroDigests(vx_ctx* ctx) : c(ctx) {}
-    const uint8_t* get(uint32_t len) const {
-        for (int k = 0; k < n_have; ++k)
-            if (have[k].len == len) return have[k].digest;
-        return nullptr;
-    }
-    int start(const uint32_t* want, int nwant) {
-        uint32_t lens[2] = {0, 0};
-        for (int k = 0; k < nwant; ++k) {
-            const auto& cache = c->holes.sha1_zero;
-            const auto it = std::find_if(cache.begin(), cache.end(), [&](const auto& e) { return e.len == want[k]; });
-            if (it != cache.end()) have[n_have++] = *it;
-            else lens[n++] = want[k];
-        }
-        if (n == 0) return 0;
-        for (int k = 0; k < n; ++k) have[n_have + k].len = lens[k];
-        const int rc = ensure_holes(c, "vx_verify_files");
-        if (rc) return n = 0, rc;
-        vx_ctx::Holes& h = c->holes;
-        std::memcpy(h.h, lens, sizeof(lens));
-        hipError_t e = hipMemcpyAsync(h.d, h.h, sizeof(lens), hipMemcpyHostToDevice, h.stream);
-        if (e == hipSuccess) e = hipEventRecord(h.t0, h.stream);
-        if (e == hipSuccess)
-            e = vx::launch_sha1_zeros(reinterpret_cast<const uint32_t*>(h.d), (uint32_t)n, h.d + h.kDigestsAt, h.stream);
-        if (e == hipSuccess) e = hipEventRecord(h.t1, h.stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(h.h + h.kDigestsAt, h.d + h.kDigestsAt, (size_t)n * 20, hipMemcpyDeviceToHost, h.stream);
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(h.stream);
-            return n = 0, hip_fail(e, "vx_verify_files: zero-piece digests");
-        }
-        return 0;
-    }
-    int wait() {
-        if (n == 0) return 0;
-        vx_ctx::Holes& h = c->holes;
-        const int launched = n;
-        n = 0;
-        if (hipStreamSynchronize(h.stream) != hipSuccess)
-            return fail(VX_EDEVICE, "vx_verify_files: zero-piece digests failed on the device");
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, h.t0, h.t1) == hipSuccess) h.last.zero_hash_ms = ms;
-        for (int k = 0; k < launched; ++k) {
-            vx_ctx::Holes::Sha1Zero& e = have[n_have++];
-            std::memcpy(e.digest, h.h + h.kDigestsAt + (size_t)k * 20, 20);
-            if (h.sha1_zero.size() >= h.kZeroCache) h.sha1_zero.erase(h.sha1_zero.begin());
-            h.sha1_zero.push_back(e);
-        }
-        return 0;
-    }
-};
-
 // Re-verify chunk size for `count` pieces: 256 KiB when
 // every piece's chunk fits one slot arena (a single window of rounds), else
 // 128 KiB.  A call split into windows ends on its last, smaller window, whose
@@ -378,7 +314,7 @@ int64_t verify_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
     c->holes.last = vx_hole_trace{};
     std::vector<uint64_t> todo;
     std::vector<uint8_t> is_hole;  // per piece of the range; empty: none is
-    ZeroDigests zero(c);
+    ZeroDigests zero(c, "vx_verify_files");
     if (!sp && !hashing) {
         const vx_extents::Holes holes = scan_holes(c, fds, file_lengths);
         if (holes.any()) {

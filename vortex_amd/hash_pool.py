@@ -457,10 +457,11 @@ class HashPool:
 
     @property
     def skip_holes(self) -> bool:
-        """Whether verify_files / verify_merkle_files judge ranges the file
-        system never wrote without reading them (vx_set_skip_holes, DESIGN.md
-        §6.11).  Off by default; the split, the hybrid and the hash calls
-        ignore it."""
+        """Whether verify_files / verify_merkle_files / verify_hybrid_files
+        judge ranges the file system never wrote without reading them
+        (vx_set_skip_holes): whole pieces (v1), 16 KiB blocks
+        (v2), 256 KiB chunks (hybrid).  Off by default; the split and the hash
+        calls ignore it."""
         return self._skip_holes
 
     @skip_holes.setter
@@ -469,10 +470,11 @@ class HashPool:
         self._skip_holes = bool(on)
 
     def last_verify_holes(self) -> dict:
-        """What the last verify_files / verify_merkle_files call skipped
-        (vx_last_verify_holes): hole_pieces, hole_blocks, hole_bytes, the
-        extents scanned, scan_ms and zero_hash_ms.  All zero with skip_holes
-        off."""
+        """What the last verify_files / verify_merkle_files /
+        verify_hybrid_files call skipped (vx_last_verify_holes): hole_pieces
+        (no byte read), hole_blocks (16 KiB blocks not read; the hybrid call
+        counts those of its hole pieces too), hole_bytes, the extents scanned,
+        scan_ms and zero_hash_ms.  All zero with skip_holes off."""
         t = _lib.vx_hole_trace()
         check(self.lib.vx_last_verify_holes(self._h, ctypes.byref(t)), "vx_last_verify_holes", self.lib)
         return {name: getattr(t, name) for name, _ in _lib.vx_hole_trace._fields_}
@@ -677,7 +679,8 @@ class HashPool:
         implied and never read; `pieces` is the v1 `pieces` table (n*20
         bytes), `roots` what verify_merkle_files takes (n*32 bytes), pieces
         numbered as hybrid.hybrid_pieces numbers them.  Every byte is read and
-        copied to the device once and feeds both hashes.  Returns one
+        copied to the device once and feeds both hashes; with skip_holes, 256
+        KiB chunks the file system never wrote are not read at all.  Returns one
         (v1_ok, v2_ok) per piece of [first, first+count); a piece that could
         not be read is (False, False) and counts in stats()["io_errors"]."""
         n = len(roots) // 32

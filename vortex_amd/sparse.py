@@ -101,6 +101,65 @@ def hole_pieces(paths, file_lengths, piece_length: int, cap: int = MAX_EXTENTS) 
     return [bool(s) and all(holes.hole(*x) for x in s) for s in segs], holes.extents
 
 
+HYBRID_CHUNK = 256 * 1024  # vx_hybrid::kChunk
+
+
+def hybrid_chunk(piece_length: int, chunk: int | None = None) -> int:
+    """The chunk of the hybrid rounds (vx_hybrid::chunk_for on a stage that
+    holds a piece): ``chunk``, or the whole piece where a piece is shorter than
+    two chunks."""
+    c = HYBRID_CHUNK if chunk is None else int(chunk)
+    return piece_length if piece_length < 2 * c else c // merkle.BLOCK * merkle.BLOCK
+
+
+def hole_chunks(paths, file_lengths, piece_length: int, chunk: int | None = None,
+                cap: int = MAX_EXTENTS) -> tuple[list[list[bool]], int]:
+    """Hybrid (``verify_hybrid_files``): (per piece of ``hybrid.hybrid_pieces``,
+    per chunk of it, whether the chunk's data bytes all lie in holes; the data
+    extents scanned over all files)."""
+    holes = Holes(paths, file_lengths, cap)
+    C = hybrid_chunk(piece_length, chunk)
+    lens, _, findex, foff = merkle.torrent_pieces(file_lengths, piece_length)
+    out = []
+    for plen, f, off in zip(lens, findex, foff):
+        out.append([holes.hole(f, off + at, min(C, plen - at)) for at in range(0, plen, C)])
+    return out, holes.extents
+
+
+def hybrid_read_bytes(paths, file_lengths, piece_length: int, chunk: int | None = None, first: int = 0,
+                      count: int | None = None, cap: int = MAX_EXTENTS) -> dict:
+    """What ``verify_hybrid_files`` reads and skips over pieces [first, first +
+    count) with ``skip_holes`` on.  Every hole chunk is skipped but those of the
+    trailing hole run of the torrent's last piece when that piece is shorter
+    than ``piece_length`` (it has no pad, so its v1 total is not the piece
+    length and no tail lane can end it) and not wholly a hole: they are read.
+    Keys: read_bytes, hole_bytes, hole_blocks, hole_pieces (no byte read),
+    zero_runs (hole chunks in front of a data chunk), extents."""
+    masks, extents = hole_chunks(paths, file_lengths, piece_length, chunk, cap)
+    C = hybrid_chunk(piece_length, chunk)
+    lens = merkle.torrent_pieces(file_lengths, piece_length)[0]
+    n = len(lens)
+    count = n - first if count is None else count
+    out = dict(read_bytes=0, hole_bytes=0, hole_blocks=0, hole_pieces=0, zero_runs=0, extents=extents)
+    for i in range(first, first + count):
+        mask, plen = list(masks[i]), lens[i]
+        t = len(mask)  # the trailing hole run is chunks [t, end)
+        while t and mask[t - 1]:
+            t -= 1
+        if 0 < t < len(mask) and i == n - 1 and plen < piece_length:
+            mask[t:] = [False] * (len(mask) - t)
+        out["hole_pieces"] += t == 0
+        out["zero_runs"] += sum(mask[:t])
+        for k, hole in enumerate(mask):
+            nbytes = min(C, plen - k * C)
+            if hole:
+                out["hole_bytes"] += nbytes
+                out["hole_blocks"] += -(-nbytes // merkle.BLOCK)
+            else:
+                out["read_bytes"] += nbytes
+    return out
+
+
 def hole_blocks(paths, file_lengths, piece_length: int, cap: int = MAX_EXTENTS) -> tuple[list[list[bool]], int]:
     """v2 (``verify_merkle_files``): (per piece of ``merkle.torrent_pieces``,
     per 16 KiB block of it, whether the block lies wholly in a hole; the data
