@@ -977,6 +977,87 @@ int vx_merkle_check_blocks(vx_ctx* ctx, const uint8_t* const* ptrs, const uint32
                            uint32_t piece_length, const uint8_t* expected_leaves, uint64_t* bad_out,
                            uint32_t* bad_counts_out, uint8_t* leaves_out);
 
+/* ---- Block checks from disk: the leaf table of a v2 torrent --------------
+ * The torrent's leaf table is its files' leaf layers back to back, in file
+ * order: file f contributes ceil(len_f / VX_MERKLE_BLOCK) rows of 32 bytes, an
+ * empty file none, and there is no padding row anywhere.  Piece i (piece j of
+ * file f, numbered as vx_merkle_verify_files numbers them) has
+ * ceil(piece_len(i) / VX_MERKLE_BLOCK) rows from row
+ *   leaf_off[f] + j * (piece_length / VX_MERKLE_BLOCK)
+ * on, leaf_off[f] being the rows of the files in front of f.  The rows of a
+ * range of pieces are one run of the table.  vx_merkle_hash_files_leaves
+ * (below, with the hash calls) makes the table; a client keeps it with its
+ * resume data and checks the files against it here.
+ *
+ * Rows of the whole table; host only, no context.  VX_EINVAL for a NULL
+ * file_lengths or a piece_length that is not a power of two from
+ * VX_MERKLE_BLOCK to 2 GiB. */
+int64_t vx_merkle_leaf_rows(const uint64_t* file_lengths, size_t nfiles, uint32_t piece_length);
+/* The kernel of the files calls on its own, on device-resident rows: n pieces
+ * whose leaf rows lie piece-major in a window, piece k's 2^log2_width rows from
+ * row row0 + (k << log2_width) on (all inside the window; 32-byte rows,
+ * d_window 16-byte aligned).  Of piece k's rows the first d_blocks[k] (1 ..
+ * 2^log2_width) are live and stand for rows d_leaf_first[k] .. of a compact
+ * leaf table.
+ *  - d_expected_leaves with d_bad (both or neither): each live row is compared
+ *    with its row of that table; block b of piece k that differs is bit b & 63
+ *    of word k * wpp + (b >> 6) of d_bad, the mapping of "The bitmap" above but
+ *    with wpp words per piece as given, wpp >= max(1, 2^log2_width / 64).  The
+ *    words (b >> 6) < max(1, 2^log2_width / 64) of every piece are written,
+ *    zeros included; words above them are left as they are.  A dead slot is
+ *    never set.
+ *  - d_shadow_out (may be NULL; needs d_expected_leaves): a second window of
+ *    the same rows; row row0 + (k << log2_width) + b gets the table's row of
+ *    block b, 32 zero bytes for a dead slot: what vx_merkle_device_nodes
+ *    reduces to tell whether the stored rows themselves belong to the piece.
+ *  - d_leaves_out (may be NULL): the compact table to write; each live window
+ *    row goes to its row of it.  Not the buffer d_expected_leaves names.
+ * All three outputs NULL is VX_EINVAL.  n << log2_width fits 32 bits.  The
+ * device-resident metadata is not checked here;
+ * vortex_amd.device.merkle_leaf_check checks it.  One launch, no atomics.
+ * Enqueue-only; n == 0 launches nothing. */
+int vx_merkle_device_leaf_check(const void* d_window, uint32_t row0, uint32_t n, uint32_t log2_width, uint32_t wpp,
+                                const uint32_t* d_leaf_first, const uint32_t* d_blocks,
+                                const void* d_expected_leaves, uint64_t* d_bad, void* d_shadow_out,
+                                void* d_leaves_out, void* stream);
+/* vx_merkle_verify_files that also says which blocks are wrong, in the same
+ * single pass over the files.  expected_leaves is the whole torrent's leaf
+ * table and leaf_rows must equal vx_merkle_leaf_rows(...) (VX_EINVAL
+ * otherwise, before anything is opened or allocated).  The return value,
+ * matched_out, vx_get_stats, vx_last_verify, VX_EBUSY and vx_set_skip_holes
+ * are exactly vx_merkle_verify_files'.  bad_out: vx_merkle_bitmap_words(
+ * n_pieces, log2(piece_length / VX_MERKLE_BLOCK)) words in the mapping of "The
+ * bitmap" above (every piece takes the full width's words, also the one piece
+ * of a small file), every word written.  bad_counts_out[i] (may be NULL): the
+ * set bits of piece i.  layer_ok_out[i] (may be NULL): 1 iff the stored leaf
+ * rows of piece i reduce to expected[32*i..]; it does not depend on the data.
+ * A piece that lacks bytes (missing, short or unreadable file) has matched 0
+ * and every one of its existing blocks set.  The stored rows of the range are
+ * held on the device for the call (1/512 of the range's bytes, VX_ENOMEM if
+ * that cannot be had; the _range form bounds it); a range of 2^32 leaf rows or
+ * more is VX_ERANGE.
+ *
+ *   matched  layer_ok  meaning
+ *   1        any       the data is good; set bits can then only name stale
+ *                      stored rows, and layer_ok is 0 if any is set
+ *   0        1         the set bits are exactly the blocks to fetch again; at
+ *                      least one bit is set
+ *   0        0         fetch the piece, or fetch its leaf layer again first */
+int64_t vx_merkle_verify_files_blocks(vx_ctx* ctx, const char* const* paths, const uint64_t* file_lengths,
+                                      size_t nfiles, uint32_t piece_length, const uint8_t* expected, size_t n_pieces,
+                                      const uint8_t* expected_leaves, uint64_t leaf_rows, uint8_t* matched_out,
+                                      uint8_t* layer_ok_out, uint64_t* bad_out, uint32_t* bad_counts_out,
+                                      uint32_t io_threads);
+/* Pieces [first, first + count) only: expected and expected_leaves are the
+ * whole tables, of which only the range's rows are read; matched_out,
+ * layer_ok_out and bad_counts_out have count entries, bad_out
+ * vx_merkle_bitmap_words(count, log2(piece_length / VX_MERKLE_BLOCK)) words. */
+int64_t vx_merkle_verify_files_blocks_range(vx_ctx* ctx, const char* const* paths, const uint64_t* file_lengths,
+                                            size_t nfiles, uint32_t piece_length, const uint8_t* expected,
+                                            size_t n_pieces, const uint8_t* expected_leaves, uint64_t leaf_rows,
+                                            size_t first, size_t count, uint8_t* matched_out, uint8_t* layer_ok_out,
+                                            uint64_t* bad_out, uint32_t* bad_counts_out, uint32_t io_threads);
+
 /* ---- Hashing: from files to `pieces`, `piece layers` and `pieces root` ---
  * Every entry above checks hashes that somebody else made.  The entries below
  * make them: what a client needs to create a torrent from a directory, and what
@@ -1102,6 +1183,25 @@ int64_t vx_merkle_hash_files(vx_ctx* ctx, const char* const* paths, const uint64
 int64_t vx_merkle_hash_files_range(vx_ctx* ctx, const char* const* paths, const uint64_t* file_lengths,
                                    size_t nfiles, uint32_t piece_length, size_t n_pieces, size_t first, size_t count,
                                    uint8_t* rows_out, uint8_t* ok_out, uint32_t io_threads);
+/* vx_merkle_hash_files that also keeps the 16 KiB leaf layer, what a seeder
+ * answers `hashes` requests at base layer 0 from and what
+ * vx_merkle_verify_files_blocks checks against: leaves_out gets the whole
+ * torrent's leaf table ("Block checks from disk" above) and leaf_rows must
+ * equal vx_merkle_leaf_rows(...) (VX_EINVAL otherwise).  The rows of a piece
+ * with ok == 0 are all zero: never a row over bytes that were not read.  The
+ * table is held on the device until the last round and comes back in one copy
+ * (VX_ENOMEM if it cannot be had, VX_ERANGE for 2^32 rows or more; the _range
+ * form bounds it).  Everything else as vx_merkle_hash_files. */
+int64_t vx_merkle_hash_files_leaves(vx_ctx* ctx, const char* const* paths, const uint64_t* file_lengths,
+                                    size_t nfiles, uint32_t piece_length, size_t n_pieces, uint8_t* rows_out,
+                                    uint8_t* ok_out, uint8_t* tree_out, uint64_t tree_rows, uint8_t* leaves_out,
+                                    uint64_t leaf_rows, uint32_t io_threads);
+/* Pieces [first, first + count) only; no tree.  leaves_out is still the whole
+ * table, of which only the range's rows are written. */
+int64_t vx_merkle_hash_files_leaves_range(vx_ctx* ctx, const char* const* paths, const uint64_t* file_lengths,
+                                          size_t nfiles, uint32_t piece_length, size_t n_pieces, size_t first,
+                                          size_t count, uint8_t* rows_out, uint8_t* ok_out, uint8_t* leaves_out,
+                                          uint64_t leaf_rows, uint32_t io_threads);
 /* Hash a hybrid torrent's files in one pass: vx_hybrid_verify_files with both
  * expected tables absent.  sha1_out[20*i..] is taken over piece i's data plus
  * its implied pad zeros, as that call defines it; rows_out, ok_out, tree_out

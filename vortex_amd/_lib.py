@@ -64,6 +64,8 @@ EXPORTS = (
     "vx_hash_files", "vx_hash_files_range", "vx_merkle_hash_files", "vx_merkle_hash_files_range",
     "vx_hybrid_hash_files", "vx_hybrid_hash_files_range",
     "vx_set_skip_holes", "vx_last_verify_holes", "vx_sha1_device_zeros", "vx_merkle_device_zero_leaves",
+    "vx_merkle_leaf_rows", "vx_merkle_device_leaf_check", "vx_merkle_verify_files_blocks",
+    "vx_merkle_verify_files_blocks_range", "vx_merkle_hash_files_leaves", "vx_merkle_hash_files_leaves_range",
 )
 # ... plus include/vx_tuning.h and include/vx_synth.h: libvortex_amd_tuning.so only.
 TUNING_EXPORTS = (
@@ -319,6 +321,17 @@ def _declare(L: ctypes.CDLL, tuning: bool = False) -> None:
                                   c.c_uint32], c.c_int64),
         "vx_merkle_hash_files_range": ([vp, vp, vp, c.c_size_t, c.c_uint32, c.c_size_t, c.c_size_t, c.c_size_t, vp,
                                         vp, c.c_uint32], c.c_int64),
+        "vx_merkle_leaf_rows": ([vp, c.c_size_t, c.c_uint32], c.c_int64),
+        "vx_merkle_device_leaf_check": ([vp, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, vp, vp, vp, vp, vp, vp,
+                                         vp], c.c_int),
+        "vx_merkle_verify_files_blocks": ([vp, vp, vp, c.c_size_t, c.c_uint32, vp, c.c_size_t, vp, c.c_uint64, vp,
+                                           vp, vp, vp, c.c_uint32], c.c_int64),
+        "vx_merkle_verify_files_blocks_range": ([vp, vp, vp, c.c_size_t, c.c_uint32, vp, c.c_size_t, vp, c.c_uint64,
+                                                 c.c_size_t, c.c_size_t, vp, vp, vp, vp, c.c_uint32], c.c_int64),
+        "vx_merkle_hash_files_leaves": ([vp, vp, vp, c.c_size_t, c.c_uint32, c.c_size_t, vp, vp, vp, c.c_uint64, vp,
+                                         c.c_uint64, c.c_uint32], c.c_int64),
+        "vx_merkle_hash_files_leaves_range": ([vp, vp, vp, c.c_size_t, c.c_uint32, c.c_size_t, c.c_size_t,
+                                               c.c_size_t, vp, vp, vp, c.c_uint64, c.c_uint32], c.c_int64),
         "vx_hybrid_hash_files": ([vp, vp, vp, c.c_size_t, c.c_uint32, c.c_size_t, vp, vp, vp, vp, c.c_uint64,
                                   c.c_uint32], c.c_int64),
         "vx_hybrid_hash_files_range": ([vp, vp, vp, c.c_size_t, c.c_uint32, c.c_size_t, c.c_size_t, c.c_size_t, vp,

@@ -269,6 +269,72 @@ __global__ __launch_bounds__(kBlock) void merkle_block_kernel(const uint8_t* __r
     if (g < n_blocks && row != kSkipRow) store_row(leaves, row, s);
 }
 
+// Leaf check (the re-verify from disk, block by block; DESIGN.md §3.7 "Block
+// checks from disk"): one launch per group of pieces a round finished, beside
+// the group's node launch.  Lane g = (k << K) + slot takes row g of `window`
+// (the group's first ring row; the group does not wrap): slot `slot` of piece
+// k, live iff slot < blocks[k]; the piece's rows of the compact leaf table
+// start at row leaf_first[k].  Nothing is hashed.
+//  * leaves_out (copy-out): a live slot's window row goes to row
+//    leaf_first[k] + slot.
+//  * expected_leaves (check; with bad_words and shadow): the stored row
+//    leaf_first[k] + slot is compared with the window row; a live slot that
+//    differs is bad, a dead one never is.  The stored row (32 zero bytes for a
+//    dead slot) also goes to row g of `shadow`, which the node kernels then
+//    reduce as they reduce the window.
+// The bitmap is merkle_block_check_kernel's, but with the caller's words per
+// piece (wpp >= max(1, 2^K / 64): a group may be narrower than the call):
+// K >= 6, a wave is 64 slots of one piece and lane 0 stores its word; K < 6, a
+// wave holds 64 >> K whole pieces and each piece's slot-0 lane stores its 2^K
+// bits.  The words of a piece that its group does not cover are not written.
+// Every word has at most one writing lane (no atomics, no LDS).
+__global__ __launch_bounds__(kBlock) void merkle_leaf_check_kernel(const uint8_t* __restrict__ window, uint32_t n,
+                                                                   uint32_t log2_width, uint32_t wpp,
+                                                                   const uint32_t* __restrict__ leaf_first,
+                                                                   const uint32_t* __restrict__ blocks,
+                                                                   const uint8_t* __restrict__ expected_leaves,
+                                                                   unsigned long long* __restrict__ bad_words,
+                                                                   uint8_t* __restrict__ shadow,
+                                                                   uint8_t* __restrict__ leaves_out) {
+    const uint32_t g = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t rows = n << log2_width;
+    // Lanes past the last row redo row rows-1 (in bounds, the wave stays
+    // convergent), store nothing and contribute 0 to the ballot.
+    const uint32_t gg = g < rows ? g : rows - 1;
+    const uint32_t piece = gg >> log2_width;
+    const uint32_t slot = gg & ((1u << log2_width) - 1);
+    const uint32_t nb = blocks[piece];  // >= 1: a piece has a byte
+    const uint32_t first = leaf_first[piece];
+    const bool live = slot < nb, mine = g < rows;
+    const uint4* w = reinterpret_cast<const uint4*>(window + (size_t)gg * 32);
+    const uint4 w0 = w[0], w1 = w[1];
+    if (leaves_out && mine && live) {
+        uint4* o = reinterpret_cast<uint4*>(leaves_out + ((size_t)first + slot) * 32);
+        o[0] = w0;
+        o[1] = w1;
+    }
+    if (!expected_leaves) return;  // (kernel-uniform)
+    // a dead slot loads the piece's last row (in bounds) and drops it
+    const uint4* x = reinterpret_cast<const uint4*>(expected_leaves + ((size_t)first + (live ? slot : nb - 1)) * 32);
+    uint4 x0 = x[0], x1 = x[1];
+    if (!live) x0 = x1 = make_uint4(0, 0, 0, 0);
+    const uint32_t diff = (x0.x ^ w0.x) | (x0.y ^ w0.y) | (x0.z ^ w0.z) | (x0.w ^ w0.w) | (x1.x ^ w1.x) |
+                          (x1.y ^ w1.y) | (x1.z ^ w1.z) | (x1.w ^ w1.w);
+    if (shadow && mine) {
+        uint4* o = reinterpret_cast<uint4*>(shadow + (size_t)gg * 32);
+        o[0] = x0;
+        o[1] = x1;
+    }
+    const unsigned long long mask = __ballot(mine && live && diff != 0);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (log2_width >= 6) {
+        // (rows is a multiple of 64: g < rows is wave-uniform)
+        if (lane == 0 && mine) bad_words[(size_t)piece * wpp + (slot >> 6)] = mask;
+    } else if (slot == 0 && mine) {
+        bad_words[(size_t)piece * wpp] = (mask >> lane) & ((1ull << (1u << log2_width)) - 1);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Node reduction.
 
@@ -811,6 +877,20 @@ hipError_t launch_merkle_blocks(const uint8_t* stage, const uint32_t* rows, cons
 hipError_t launch_merkle_nodes(const uint8_t* leaves, const uint8_t* log2w, uint32_t n, uint32_t log2_width,
                                uint8_t* roots, const uint8_t* expected, uint8_t* matched, hipStream_t stream) {
     return launch_nodes(n, log2_width, leaves, log2w, roots, expected, matched, stream);
+}
+
+hipError_t launch_merkle_leaf_check(const uint8_t* window, uint32_t row0, uint32_t n, uint32_t log2_width,
+                                    uint32_t wpp, const uint32_t* leaf_first, const uint32_t* blocks,
+                                    const uint8_t* expected_leaves, uint64_t* bad, uint8_t* shadow,
+                                    uint8_t* leaves_out, hipStream_t stream) {
+    if (n == 0 || (!expected_leaves && !leaves_out)) return hipSuccess;
+    const uint64_t rows = (uint64_t)n << log2_width;
+    const uint32_t grid = (uint32_t)((rows + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(merkle_leaf_check_kernel, dim3(grid), dim3(kBlock), 0, stream, window + (size_t)row0 * 32, n,
+                       log2_width, wpp, leaf_first, blocks, expected_leaves,
+                       reinterpret_cast<unsigned long long*>(bad), shadow ? shadow + (size_t)row0 * 32 : nullptr,
+                       leaves_out);
+    return hipGetLastError();
 }
 
 hipError_t launch_merkle_root(const uint8_t* layer, uint32_t n, uint8_t* work, uint8_t* root,

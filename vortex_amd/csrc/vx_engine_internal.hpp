@@ -316,6 +316,18 @@ struct vx_ctx {
         uint8_t* d_call = nullptr;
         uint64_t call_cap = 0;
         hipEvent_t chain = nullptr;
+        // ... of the calls that keep or check the leaf layer (DESIGN.md §3.7
+        // "Block checks from disk"): the range's rows of the leaf table, the
+        // shadow window (the stored rows where the leaf window has the data's),
+        // per piece leaf_first | blocks | layer_ok, and the range's bitmap.
+        uint8_t* d_leaf = nullptr;
+        uint64_t leaf_cap = 0;  // rows
+        uint8_t* d_shadow = nullptr;
+        uint64_t shadow_rows = 0;
+        uint8_t* d_piece = nullptr;
+        uint64_t piece_cap = 0;  // pieces, 9 bytes each
+        uint64_t* d_bad = nullptr;
+        uint64_t bad_cap = 0;  // words
     } mfiles;
     uint64_t verify_t0_ns = 0;                // the running re-verify call's start (steady clock)
     // Skipping file holes in the re-verify (vx_set_skip_holes, DESIGN.md

@@ -173,6 +173,19 @@ hipError_t launch_merkle_blocks(const uint8_t* stage, const uint32_t* rows, cons
                                 uint8_t* leaves, hipStream_t stream);
 hipError_t launch_merkle_nodes(const uint8_t* leaves, const uint8_t* log2w, uint32_t n, uint32_t log2_width,
                                uint8_t* roots, const uint8_t* expected, uint8_t* matched, hipStream_t stream);
+// The leaf check (merkle_leaf_check_kernel, DESIGN.md §3.7 "Block checks from
+// disk"): the n pieces of one vx_merkle::Nodes entry, piece k's 2^log2_width
+// rows at row row0 + (k << log2_width) of window; blocks[k] of them are live
+// and belong at row leaf_first[k] on of the compact leaf table.  With
+// expected_leaves (and bad; shadow may be NULL): the live rows against that
+// table, piece k's bits into words bad[k * wpp ..] (wpp >= max(1,
+// 2^log2_width / 64); words the group does not cover are left alone), and the
+// stored rows, zeros at dead slots, into shadow at the window's rows.  With
+// leaves_out: the live rows into that table.  Neither: nothing is launched.
+hipError_t launch_merkle_leaf_check(const uint8_t* window, uint32_t row0, uint32_t n, uint32_t log2_width,
+                                    uint32_t wpp, const uint32_t* leaf_first, const uint32_t* blocks,
+                                    const uint8_t* expected_leaves, uint64_t* bad, uint8_t* shadow,
+                                    uint8_t* leaves_out, hipStream_t stream);
 // Leaf rows of unwritten blocks (merkle_zero_leaf_kernel):
 // SHA-256 of lens[j] (1..16384) zero bytes into leaf row rows[j] (NULL: j),
 // nothing read but the tables.  full_row (host, 32 bytes, may be NULL): the row

@@ -625,6 +625,94 @@ def merkle_nodes(leaves: torch.Tensor, n: int, log2_width: int, log2w: Optional[
     return roots, matched
 
 
+def merkle_leaf_check(window: torch.Tensor, row0: int, n: int, log2_width: int, leaf_first: torch.Tensor,
+                      blocks: torch.Tensor, expected_leaves: Optional[torch.Tensor] = None,
+                      bad: Optional[torch.Tensor] = None, wpp: Optional[int] = None,
+                      shadow: Optional[torch.Tensor] = None, leaves_out: Optional[torch.Tensor] = None,
+                      stream: Optional[torch.cuda.Stream] = None, validate: bool = True):
+    """The leaf check of the files calls on its own (vx_merkle_device_leaf_check):
+    n pieces whose leaf rows lie in `window` ([R,32] uint8), piece k's
+    2^log2_width rows from row row0 + (k << log2_width) on; the first blocks[k]
+    of them are live and stand for rows leaf_first[k].. of a compact leaf table
+    (leaf_first, blocks: int32 [n]).
+
+    expected_leaves ([T,32]): each live row is compared with its row of that
+    table into `bad` (int64, the bitmap's uint64 words bit for bit; n * wpp
+    words, wpp defaulting to max(1, 2^log2_width / 64); made zeroed if not
+    given): block b of piece k is bit b & 63 of word k * wpp + (b >> 6); words
+    above a piece's max(1, 2^log2_width / 64) stay as they were.  shadow (a
+    tensor as large as window, needs expected_leaves): gets the table's rows at
+    the window's rows, zeros at dead slots.  leaves_out ([T,32]): each live
+    window row goes to its row of it.  Returns (bad, shadow, leaves_out).
+
+    validate (default): 1 <= blocks[k] <= 2^log2_width and every table row
+    inside expected_leaves / leaves_out, checked on the device with one copy
+    back (a sync).  Enqueue-only otherwise."""
+    _req(window, "window")
+    _req(leaf_first, "leaf_first", torch.int32)
+    _req(blocks, "blocks", torch.int32)
+    if not 0 <= log2_width <= 17:
+        raise ValueError("log2_width must be 0..17")
+    if n < 0 or row0 < 0 or leaf_first.numel() != n or blocks.numel() != n:
+        raise ValueError("leaf_first and blocks must hold n entries; n and row0 must be >= 0")
+    rows = n << log2_width
+    if (row0 + rows) >> 32:
+        raise ValueError("row0 + (n << log2_width) must fit 32 bits")
+    if window.numel() < 32 * (row0 + rows):
+        raise ValueError("the pieces' rows end past the window")
+    need = max(1, (1 << log2_width) // 64)
+    wpp = need if wpp is None else wpp
+    if wpp < need:
+        raise ValueError("wpp must be at least max(1, 2^log2_width / 64)")
+    if expected_leaves is None and leaves_out is None:
+        raise ValueError("merkle_leaf_check: neither expected_leaves nor leaves_out asked for")
+    if expected_leaves is None and (bad is not None or shadow is not None):
+        raise ValueError("bad and shadow need expected_leaves")
+    dev = window.device
+    for name, t in (("leaf_first", leaf_first), ("blocks", blocks), ("expected_leaves", expected_leaves),
+                    ("bad", bad), ("shadow", shadow), ("leaves_out", leaves_out)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, window on {dev}")
+    table_rows = None
+    for name, t in (("expected_leaves", expected_leaves), ("leaves_out", leaves_out)):
+        if t is not None:
+            _req(t, name)
+            if t.numel() % 32:
+                raise ValueError(f"{name} must hold whole 32-byte rows")
+            table_rows = t.numel() // 32 if table_rows is None else min(table_rows, t.numel() // 32)
+    if expected_leaves is not None and leaves_out is not None and expected_leaves.data_ptr() == leaves_out.data_ptr():
+        raise ValueError("leaves_out and expected_leaves must be different tensors")
+    if expected_leaves is not None:
+        if bad is None:
+            bad = torch.zeros((n * wpp,), dtype=torch.int64, device=dev)
+        else:
+            _req(bad, "bad", torch.int64)
+            if bad.numel() < n * wpp:
+                raise ValueError("bad must hold n * wpp words")
+    if shadow is not None:
+        _req(shadow, "shadow")
+        if shadow.numel() < 32 * (row0 + rows):
+            raise ValueError("shadow must be as large as the window's rows in use")
+    if validate and n:
+        ends = leaf_first.to(torch.int64) + blocks.to(torch.int64)
+        stats = torch.stack([blocks.min().to(torch.int64), blocks.max().to(torch.int64),
+                             leaf_first.min().to(torch.int64), ends.max()]).cpu().tolist()
+        if stats[0] < 1 or stats[1] > 1 << log2_width:
+            raise ValueError("merkle_leaf_check: every blocks[k] must lie in 1..2^log2_width")
+        if stats[2] < 0 or stats[3] > table_rows:
+            raise ValueError(f"merkle_leaf_check: a piece's rows end at table row {stats[3]}, the table holds "
+                             f"{table_rows}")
+    rc = lib().vx_merkle_device_leaf_check(window.data_ptr(), row0, n, log2_width, wpp, leaf_first.data_ptr(),
+                                           blocks.data_ptr(),
+                                           expected_leaves.data_ptr() if expected_leaves is not None else None,
+                                           bad.data_ptr() if bad is not None else None,
+                                           shadow.data_ptr() if shadow is not None else None,
+                                           leaves_out.data_ptr() if leaves_out is not None else None,
+                                           _stream_ptr(stream, dev))
+    check(rc, "vx_merkle_device_leaf_check")
+    return bad, shadow, leaves_out
+
+
 def merkle_root(layer: torch.Tensor, height: int = 0, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
     """Root of a layer of hashes ([n,32] uint8) standing `height` levels above
     the leaves, padded to a power of two with pad hashes

@@ -71,6 +71,26 @@ class DownloadedHybridPiece:
         return self.matched == 3
 
 
+@dataclass
+class BlockVerdicts:
+    """What HashPool.verify_merkle_files_blocks returns for a range of pieces;
+    unpacks as (matched, layer_ok, bad, bad_counts)."""
+
+    matched: list
+    layer_ok: list
+    bad: list  # the bitmap's uint64 words, len(bad) / len(matched) per piece
+    bad_counts: list
+    io_errors: int = 0
+
+    def __iter__(self):
+        return iter((self.matched, self.layer_ok, self.bad, self.bad_counts))
+
+    def blocks(self, i: int) -> list:
+        """The set blocks of piece i of the range, in order."""
+        wpp = len(self.bad) // max(1, len(self.matched))
+        return [64 * k + b for k in range(wpp) for b in range(64) if self.bad[i * wpp + k] >> b & 1]
+
+
 def _addr_of(buf) -> tuple[int, Any]:
     """Stable address of a writable or read-only buffer plus a keep-alive."""
     if isinstance(buf, (bytes,)):
@@ -755,6 +775,87 @@ class HashPool:
         bad = check(rc, "vx_merkle_hash_files", self.lib)
         return (rows.raw[:32 * count], [bool(b) for b in ok.raw[:count]],
                 tree.raw[:32 * tree_rows] if tree is not None else None, int(bad))
+
+    def hash_merkle_files_leaves(self, paths: Sequence[str], file_lengths: Sequence[int], piece_length: int,
+                                 io_threads: int = 0, first: int = 0, count: int | None = None,
+                                 trees: bool = True) -> tuple[bytes, list[bool], Optional[bytes], int, bytes]:
+        """hash_merkle_files that also keeps the 16 KiB leaf layer
+        (vx_merkle_hash_files_leaves), in the same pass.  Returns (rows, ok,
+        tree, pieces with I/O errors, leaves): the first four as
+        hash_merkle_files; leaves is the torrent's leaf table, laid out by
+        merkle.leaf_layout (merkle.file_leaf_table is its model): what a seeder
+        answers `hashes` requests at base layer 0 from and what
+        verify_merkle_files_blocks takes.  A piece that could not be read has
+        zero leaf rows.  A range call (first/count) returns the rows of its
+        pieces only: rows [leaf_first[first], leaf_first[first + count - 1] +
+        blocks[first + count - 1]) of the table."""
+        leaf_first, blocks, leaf_rows = merkle.leaf_layout(file_lengths, piece_length)
+        n = len(leaf_first)
+        if count is None:
+            count = n - first
+        arr, lens = _path_arrays(paths, file_lengths)
+        rows = ctypes.create_string_buffer(32 * max(1, count))
+        ok = ctypes.create_string_buffer(max(1, count))
+        leaves = ctypes.create_string_buffer(32 * max(1, leaf_rows))
+        tree = None
+        if first == 0 and count == n:
+            tree_rows = merkle.tree_layout(file_lengths, piece_length)[1][-1] if trees else 0
+            tree = ctypes.create_string_buffer(32 * max(1, tree_rows)) if trees else None
+            rc = self.lib.vx_merkle_hash_files_leaves(self._h, arr, lens, len(paths), piece_length, n, rows, ok, tree,
+                                                      tree_rows, leaves, leaf_rows, io_threads)
+        else:
+            rc = self.lib.vx_merkle_hash_files_leaves_range(self._h, arr, lens, len(paths), piece_length, n, first,
+                                                            count, rows, ok, leaves, leaf_rows, io_threads)
+        bad = check(rc, "vx_merkle_hash_files_leaves", self.lib)
+        lo, hi = (leaf_first[first], leaf_first[first + count - 1] + blocks[first + count - 1]) if count else (0, 0)
+        return (rows.raw[:32 * count], [bool(b) for b in ok.raw[:count]],
+                tree.raw[:32 * tree_rows] if tree is not None else None, int(bad), leaves.raw[32 * lo:32 * hi])
+
+    def verify_merkle_files_blocks(self, paths: Sequence[str], file_lengths: Sequence[int], piece_length: int,
+                                   expected: bytes, leaves: bytes, first: int | None = None,
+                                   count: int | None = None, io_threads: int = 0) -> "BlockVerdicts":
+        """verify_merkle_files that also says which 16 KiB blocks are wrong, in
+        the same single pass (vx_merkle_verify_files_blocks).  `leaves` is the
+        torrent's stored leaf table (hash_merkle_files_leaves, or a client's
+        resume data; merkle.leaf_layout).  Returns BlockVerdicts(matched,
+        layer_ok, bad, bad_counts, io_errors) over pieces [first, first +
+        count): matched as verify_merkle_files; layer_ok[i] whether the stored
+        leaf rows of piece i reduce to its expected row (it does not depend on
+        the data); bad the bitmap's uint64 words, merkle.bitmap_words(count,
+        log2_width(piece_length)) of them, block b of piece i being bit b & 63
+        of word i * wpp + (b >> 6) (BlockVerdicts.blocks(i) lists them);
+        bad_counts[i] the set bits of piece i.
+
+        matched: the data is good, and set bits can only name stale stored
+        rows (layer_ok is then False).  Not matched and layer_ok: the set bits
+        are exactly the blocks to fetch again.  Neither: fetch the piece, or
+        its leaf layer first.  A piece that lacks bytes has every existing
+        block set."""
+        n = len(expected) // 32
+        first = 0 if first is None else first
+        if count is None:
+            count = n - first
+        lw = merkle.log2_width(piece_length)
+        if len(leaves) % 32:
+            raise ValueError("leaves must hold whole 32-byte rows")
+        arr, lens = _path_arrays(paths, file_lengths)
+        exp = ctypes.create_string_buffer(bytes(expected), max(1, len(expected)))
+        tab = ctypes.create_string_buffer(bytes(leaves), max(1, len(leaves)))
+        words = merkle.bitmap_words(max(count, 0), lw)
+        out = ctypes.create_string_buffer(max(1, count))
+        layer = ctypes.create_string_buffer(max(1, count))
+        bad = (ctypes.c_uint64 * max(1, words))()
+        counts = (ctypes.c_uint32 * max(1, count))()
+        if first == 0 and count == n:
+            rc = self.lib.vx_merkle_verify_files_blocks(self._h, arr, lens, len(paths), piece_length, exp, n, tab,
+                                                        len(leaves) // 32, out, layer, bad, counts, io_threads)
+        else:
+            rc = self.lib.vx_merkle_verify_files_blocks_range(self._h, arr, lens, len(paths), piece_length, exp, n,
+                                                              tab, len(leaves) // 32, first, count, out, layer, bad,
+                                                              counts, io_threads)
+        errs = check(rc, "vx_merkle_verify_files_blocks", self.lib)
+        return BlockVerdicts([bool(b) for b in out.raw[:count]], [bool(b) for b in layer.raw[:count]],
+                             list(bad[:words]), list(counts[:count]), int(errs))
 
     def hash_hybrid_files(self, paths: Sequence[str], file_lengths: Sequence[int], piece_length: int,
                           io_threads: int = 0, first: int = 0, count: int | None = None,

@@ -257,6 +257,39 @@ def bad_blocks(data, expected_leaves) -> list[int]:
             if hashlib.sha256(data[b * BLOCK:(b + 1) * BLOCK]).digest() != rows[b]]
 
 
+def leaf_layout(file_lengths, piece_length: int) -> tuple[list[int], list[int], int]:
+    """(leaf_first, blocks, rows) of a torrent's leaf table (vx_hash.h, "Block
+    checks from disk"): the files' leaf layers back to back in file order, file
+    f contributing ceil(len_f / 16 KiB) rows, with no padding row anywhere.
+    Piece i (the numbering of :func:`torrent_pieces`) has blocks[i] rows from
+    row leaf_first[i] on; rows is the whole table's count
+    (vx_merkle_leaf_rows)."""
+    width = 1 << log2_width(piece_length)
+    leaf_first: list[int] = []
+    blocks: list[int] = []
+    off = 0
+    for length in file_lengths:
+        lens, _ = file_pieces(int(length), piece_length)
+        leaf_first += [off + j * width for j in range(len(lens))]
+        blocks += [(n + BLOCK - 1) // BLOCK for n in lens]
+        off += (int(length) + BLOCK - 1) // BLOCK
+    return leaf_first, blocks, off
+
+
+def file_leaf_table(paths, file_lengths, piece_length: int) -> bytes:
+    """The leaf table of a torrent's files with hashlib: SHA-256 of every 16
+    KiB block of every file (a file's last block at its real length), laid out
+    by :func:`leaf_layout`.  The model of ``HashPool.hash_merkle_files_leaves``
+    and what ``HashPool.verify_merkle_files_blocks`` takes."""
+    log2_width(piece_length)
+    out = []
+    for path, length in zip(paths, file_lengths):
+        with open(path, "rb") as f:
+            for o in range(0, int(length), BLOCK):
+                out.append(hashlib.sha256(f.read(min(BLOCK, int(length) - o))).digest())
+    return b"".join(out)
+
+
 def block_proof(leaves, file_tree: bytes, m: int, height: int, piece: int, pos: int, span: int) -> bytes:
     """The `hashes` message for a base-layer-0 request of `span` leaf hashes (a
     power of two) at span number `pos` inside piece `piece` of a file: `leaves`
