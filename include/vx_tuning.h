@@ -72,6 +72,12 @@ int vx_tuning_chunk_kernel(const void* d_base, const uint64_t* d_offsets, const 
  * row.  The d_pids of a launch are distinct.  Enqueue-only on `stream`. */
 int vx_tuning_zero_run_kernel(const uint32_t* d_pids, const uint32_t* d_poffs, const uint32_t* d_blocks, uint32_t n,
                               uint32_t* d_states, void* stream);
+/* merkle_zero_leaf_kernel on its own: leaf row d_rows[j] (NULL: row j) of d_leaves =
+ * SHA-256 of d_lens[j] zero bytes, d_lens[j] in 1..16384; full_row (HOST, 32 bytes, may be
+ * NULL): stored as is where d_lens[j] == 16384.  The d_rows of a launch are distinct.
+ * Enqueue-only on `stream`. */
+int vx_tuning_zero_leaf_kernel(const uint32_t* d_rows, const uint32_t* d_lens, uint32_t n,
+                               void* d_leaves, const void* full_row, void* stream);
 /* The kernel that ends a hybrid download slot on its own (DESIGN.md §3.8,
  * §6.9; tests/test_gpu_hybrid_tail_sweep.py): lane j with d_pads[j] != 0
  * finishes its piece as the zero-tail kernel does (every padded piece is

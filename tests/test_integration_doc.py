@@ -57,9 +57,13 @@ def norm_c(t: str) -> str:
     return " ".join(out)
 
 
-def c_prototypes():
-    text = open(os.path.join(ROOT, "include", "vx_hash.h")).read()
+def c_prototypes(headers=("vx_hash.h",)):
+    """{name: (return type, [argument types])} of every prototype in the
+    headers, in norm_c's form (tests/test_binding_cpu.py reads the tuning
+    headers with it too)."""
+    text = "\n".join(open(os.path.join(ROOT, "include", h)).read() for h in headers)
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)  # preprocessor lines
     protos = {}
     for m in re.finditer(r"([\w\s\*]+?)\b(vx_\w+)\s*\(([^;{]*?)\)\s*;", text):
         ret, name, args = m.group(1), m.group(2), m.group(3)

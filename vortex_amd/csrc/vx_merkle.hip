@@ -378,6 +378,20 @@ int vx_merkle_device_zero_leaves(const uint32_t* d_lens, uint32_t n, void* d_lea
     return 0;
 }
 
+int vx_tuning_zero_leaf_kernel(const uint32_t* d_rows, const uint32_t* d_lens, uint32_t n, void* d_leaves,
+                               const void* full_row, void* stream) {
+    if (n == 0) return 0;
+    if (!d_lens || !d_leaves) return fail(VX_EINVAL, "vx_tuning_zero_leaf_kernel: NULL argument");
+    if (((reinterpret_cast<uintptr_t>(d_lens) | reinterpret_cast<uintptr_t>(d_rows)) & 3) ||
+        (reinterpret_cast<uintptr_t>(d_leaves) & 15))
+        return fail(VX_EINVAL,
+                    "vx_tuning_zero_leaf_kernel: d_rows and d_lens must be 4-byte and d_leaves 16-byte aligned");
+    hipError_t e = vx::launch_merkle_zero_leaves(d_rows, d_lens, n, static_cast<uint8_t*>(d_leaves),
+                                                 static_cast<const uint8_t*>(full_row),
+                                                 static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : hip_fail(e, "vx_tuning_zero_leaf_kernel");
+}
+
 // ---- `piece layers` and hash proofs in batches ----
 
 int vx_merkle_layers_plan(const uint32_t* counts, uint32_t n_layers, struct vx_merkle_layers_plan* plan,

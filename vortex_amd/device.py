@@ -942,6 +942,8 @@ def synth_fill(data: torch.Tensor, n: int, piece_len: int, stride: Optional[int]
     include/vx_synth.h, a test/bench generator: tuning build only)."""
     _req(data, "data")
     stride = piece_len if stride is None else stride
+    if n > 0 and (n - 1) * stride + piece_len > data.numel():
+        raise ValueError("batch exceeds data tensor")
     rc = tuning().vx_synth_fill(data.data_ptr(), stride, piece_len, n, first, seed, corrupt_every,
                                 _stream_ptr(stream, data.device))
     check(rc, "vx_synth_fill", tuning())
