@@ -108,6 +108,18 @@ void vx_tuning_verify_copy_stream(struct vx_ctx* ctx, int mode);
  * 2 MiB-aligned transparent-huge-page mappings registered with hipHostRegister,
  * 0 with hipHostMalloc.  Idle stages are freed and reallocated on next use. */
 void vx_tuning_stage_huge(struct vx_ctx* ctx, int on);
+/* What the engine holds of the runtime in this process, over every context:
+ * four counts: out[0] device blocks, out[1] pinned blocks (stages included), out[2] streams,
+ * out[3] events.  Everything the engine owns is counted where it is made and
+ * where it is given back, so a context that is destroyed leaves the counts as
+ * they were before it was created. */
+void vx_tuning_live_resources(uint64_t* out);
+/* Fault injection for tests, process-wide as the counts are: after n more
+ * successful creations of a block, stream or event, the next one fails on the
+ * host before the runtime is asked (the call returns VX_ENOMEM or VX_EDEVICE as
+ * it does when the runtime refuses), and the hook turns itself off.  n < 0
+ * turns it off. */
+void vx_tuning_fail_alloc_after(int64_t n);
 /* A/B of the split's rules for pieces of one chunk (vx_verify_files_split,
  * DESIGN.md §6.6): one_round = 1 (the default) lets their groups keep the
  * first group's rule until the rates are in, skips the tenth rule and reads

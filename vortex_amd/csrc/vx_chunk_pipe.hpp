@@ -80,10 +80,8 @@ struct ChunkPipe {
         if (!c->copy_stream) {
             int least = 0, greatest = 0;
             if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess ||
-                hipStreamCreateWithPriority(&c->copy_stream, hipStreamNonBlocking, greatest) != hipSuccess) {
-                c->copy_stream = nullptr;
+                !c->copy_stream.make_with_priority(hipStreamNonBlocking, greatest))
                 return fail(VX_EDEVICE, "chunk rounds: copy stream creation failed");
-            }
         }
         cs = c->copy_stream;
         return 0;
@@ -95,21 +93,18 @@ struct ChunkPipe {
     // expected: count x 20 bytes or NULL (digests only).
     int open(uint64_t count, const uint8_t* expected, const char* who) {
         cnt = count;
-        if (c->chunk_rows_cap < count) {
-            if (c->d_chunk_rows) (void)hipFree(c->d_chunk_rows);
-            c->d_chunk_rows = nullptr;
-            c->chunk_rows_cap = 0;
-            const uint64_t cap = std::max<uint64_t>(count, 4096);
-            if (hipMalloc(&c->d_chunk_rows, cap * 61 + 256) != hipSuccess)
-                return fail(VX_ENOMEM, std::string(who) + ": device allocation failed");
-            c->chunk_rows_cap = cap;
+        if (c->chunk_rows_cap < count) {  // kept across calls: grown only when too small, never reset
+            const uint64_t grown = std::max<uint64_t>(count, 4096);
+            c->chunk_rows_cap = c->d_chunk_rows.reserve(grown * 61 + 256) ? grown : 0;
+            if (!c->chunk_rows_cap) return fail(VX_ENOMEM, std::string(who) + ": device allocation failed");
         }
         const uint64_t cap = c->chunk_rows_cap;
-        d_states = reinterpret_cast<uint32_t*>(c->d_chunk_rows);
-        d_dig = c->d_chunk_rows + cap * 20;
-        d_exp = expected ? c->d_chunk_rows + cap * 40 : nullptr;
-        d_match = expected ? c->d_chunk_rows + cap * 60 : nullptr;
-        if (!c->chunk_prev && hipEventCreateWithFlags(&c->chunk_prev, hipEventDisableTiming) != hipSuccess)
+        uint8_t* const rows = c->d_chunk_rows.get();
+        d_states = c->d_chunk_rows.as<uint32_t>();
+        d_dig = rows + cap * 20;
+        d_exp = expected ? rows + cap * 40 : nullptr;
+        d_match = expected ? rows + cap * 60 : nullptr;
+        if (!c->chunk_prev && !c->chunk_prev.make(hipEventDisableTiming))
             return fail(VX_EDEVICE, std::string(who) + ": event creation failed");
         prev_kernel = c->chunk_prev;
         if (expected && hipMemcpy(d_exp, expected, cnt * 20, hipMemcpyHostToDevice) != hipSuccess)
@@ -219,7 +214,7 @@ struct ChunkPipe {
         return rc;
     }
 
-    // The rows and the event belong to the context (freed by vx_destroy);
+    // The rows and the event belong to the context (they go with it);
     // only make sure nothing of this call is still running.
     void release() {
         if (cs) (void)hipStreamSynchronize(cs);  // data copies of this call's rounds
@@ -240,7 +235,7 @@ private:
             rc = fail(VX_EDEVICE, "chunk round: injected launch failure (vx_tuning_fail_launch_after)");
 #endif
         if (!rc) {
-            hipError_t e = vx::launch_chunk(s.d_arena, s.d_offsets, s.d_lens, m, s.d_pidx, s.d_poff, s.d_tlen,
+            hipError_t e = vx::launch_chunk(s.d_arena.get(), s.d_offsets, s.d_lens, m, s.d_pidx, s.d_poff, s.d_tlen,
                                             d_states, d_dig, d_exp, d_match, st);
             if (e != hipSuccess) rc = hip_fail(e, "chunk kernel launch");
         }
@@ -321,7 +316,7 @@ struct RoundTimeline {
 
     RoundTimeline(vx_ctx* ctx, ChunkPipe& pipe, const char* who)
         : c(ctx), cp(pipe), h2d_failed(std::string(who) + ": chunk H2D failed") {
-        if (c->anchor_ev || hipEventCreate(&c->anchor_ev) == hipSuccess) {
+        if (c->anchor_ev || c->anchor_ev.make(hipEventDefault)) {  // (timed)
             anchored = hipEventRecord(c->anchor_ev, c->slots[0].stream) == hipSuccess;
             t_anchor = vx_files::Readers::now_ns();
         }
@@ -335,12 +330,12 @@ struct RoundTimeline {
         return [this](Slot& sl, hipStream_t st) {
             bool ev = true;
             while (ev && c->copy_ev.size() < 3 * timed + 3) {
-                hipEvent_t e = nullptr;
-                ev = hipEventCreate(&e) == hipSuccess;
-                if (ev) c->copy_ev.push_back(e);
+                Event e;
+                ev = e.make(hipEventDefault);  // (timed)
+                if (ev) c->copy_ev.push_back(std::move(e));
             }
             ev = ev && hipEventRecord(c->copy_ev[3 * timed], st) == hipSuccess;
-            if (hipMemcpyAsync(sl.d_arena, sl.h_stage, sl.bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+            if (hipMemcpyAsync(sl.d_arena.get(), sl.stage.get(), sl.bytes, hipMemcpyHostToDevice, st) != hipSuccess)
                 return fail(VX_EDEVICE, h2d_failed);
             if (ev && hipEventRecord(c->copy_ev[3 * timed + 1], st) == hipSuccess) {
                 timed_bytes.push_back(sl.bytes);

@@ -28,6 +28,89 @@
 // vx_merkle.hip, hybrid torrents vx_hybrid.hip (DESIGN.md "Host engine").
 #include "vx_chunk_pipe.hpp"
 
+#ifdef VX_TEST_HOOKS
+#include <atomic>
+#endif
+
+// The handles' backend over HIP (vx_resources.hpp): the only place the engine
+// allocates or frees device or pinned memory, creates or destroys a stream or
+// an event, or registers a stage.  The test build counts what is alive
+// (vx_tuning_live_resources) and can fail a creation before the runtime is
+// asked (vx_tuning_fail_alloc_after): process-wide, so file-scope atomics (the
+// _multi calls run one thread per context), not context members.
+namespace vx_res::backend {
+
+enum Counted { kDevice, kPinned, kStreams, kEvents };
+#ifdef VX_TEST_HOOKS
+static std::atomic<int64_t> g_live[4];
+static std::atomic<int64_t> g_fail_alloc_after{-1};
+// true: this creation is the injected failure (which disarms the hook)
+static bool injected_failure() {
+    int64_t left = g_fail_alloc_after.load();
+    while (left >= 0)
+        if (g_fail_alloc_after.compare_exchange_weak(left, left - 1)) return left == 0;
+    return false;
+}
+static void count(Counted what, int by) { g_live[what] += by; }
+#else
+static bool injected_failure() { return false; }
+static void count(Counted, int) {}
+#endif
+void* device_alloc(uint64_t bytes) {
+    void* p = nullptr;
+    if (injected_failure() || hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+    count(kDevice, +1);
+    return p;
+}
+void device_free(void* p) {
+    (void)hipFree(p);
+    count(kDevice, -1);
+}
+void* pinned_alloc(uint64_t bytes) {
+    void* p = nullptr;
+    if (injected_failure() || hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) return nullptr;
+    count(kPinned, +1);
+    return p;
+}
+void pinned_free(void* p) {
+    (void)hipHostFree(p);
+    count(kPinned, -1);
+}
+hipEvent_t event_create(unsigned flags) {
+    hipEvent_t e = nullptr;
+    if (injected_failure() || hipEventCreateWithFlags(&e, flags) != hipSuccess) return nullptr;
+    count(kEvents, +1);
+    return e;
+}
+void event_destroy(hipEvent_t e) {
+    (void)hipEventDestroy(e);
+    count(kEvents, -1);
+}
+hipStream_t stream_create(unsigned flags, const int* priority) {
+    hipStream_t s = nullptr;
+    if (injected_failure() || (priority ? hipStreamCreateWithPriority(&s, flags, *priority)
+                                        : hipStreamCreateWithFlags(&s, flags)) != hipSuccess)
+        return nullptr;
+    count(kStreams, +1);
+    return s;
+}
+void stream_synchronize(hipStream_t s) { (void)hipStreamSynchronize(s); }
+void stream_destroy(hipStream_t s) {
+    (void)hipStreamDestroy(s);
+    count(kStreams, -1);
+}
+bool stage_register(void* p, uint64_t bytes) {
+    if (injected_failure() || hipHostRegister(p, bytes, hipHostRegisterDefault) != hipSuccess) return false;
+    count(kPinned, +1);
+    return true;
+}
+void stage_unregister(void* p) {
+    (void)hipHostUnregister(p);
+    count(kPinned, -1);
+}
+
+}  // namespace vx_res::backend
+
 namespace vxe {
 
 thread_local std::string g_err;
@@ -72,85 +155,21 @@ bool is_registered(const vx_ctx* c, const void* p, size_t len, const uint8_t** d
     return true;
 }
 
-// Pinned stage memory.  huge: an anonymous mapping aligned to 2 MiB with
-// MADV_HUGEPAGE, faulted in, then registered (hipHostRegister), so the
-// readers' O_DIRECT reads and the H2D copies touch 512x fewer page-table and
-// IOMMU entries than with hipHostMalloc's 4 KiB pages.
-uint8_t* alloc_stage(uint64_t bytes, bool huge, uint64_t* mapped) {
-    *mapped = 0;
-    if (!huge) {
-        uint8_t* p = nullptr;
-        return hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess ? p : nullptr;
-    }
-    constexpr uint64_t kHuge = 2ull << 20;
-    const uint64_t len = (bytes + kHuge - 1) / kHuge * kHuge;
-    void* raw = mmap(nullptr, len + kHuge, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-    if (raw == MAP_FAILED) return nullptr;
-    const uintptr_t r = reinterpret_cast<uintptr_t>(raw), a = (r + kHuge - 1) / kHuge * kHuge;
-    if (a > r) munmap(raw, a - r);  // trim to the aligned [a, a + len)
-    if (r + len + kHuge > a + len) munmap(reinterpret_cast<void*>(a + len), r + len + kHuge - (a + len));
-    uint8_t* p = reinterpret_cast<uint8_t*>(a);
-    (void)madvise(p, len, MADV_HUGEPAGE);  // a hint: 4 KiB pages where THP is off
-    // A client that forks (hooks, helpers) must not turn the pinned pages
-    // copy-on-write in the parent: the GPU keeps DMAing to the pinned page
-    // while a write after the fork would move the parent to a new one.
-    (void)madvise(p, len, MADV_DONTFORK);
-    for (uint64_t o = 0; o < len; o += 4096) p[o] = 0;
-    if (hipHostRegister(p, len, hipHostRegisterDefault) != hipSuccess) {
-        munmap(p, len);
-        return nullptr;
-    }
-    *mapped = len;
-    return p;
-}
-
-void free_stage(Slot& s) {
-    if (!s.h_stage) return;
-    if (s.stage_map) {
-        (void)hipHostUnregister(s.h_stage);
-        munmap(s.h_stage, s.stage_map);
-    } else {
-        (void)hipHostFree(s.h_stage);
-    }
-    s.h_stage = nullptr;
-    s.stage_map = 0;
-}
-
-int free_slot_mem(Slot& s) {
-    if (s.stream) (void)hipStreamSynchronize(s.stream);
-    if (s.done) (void)hipEventDestroy(s.done);
-    if (s.copied) (void)hipEventDestroy(s.copied);
-    if (s.stream) (void)hipStreamDestroy(s.stream);
-    if (s.d_arena) (void)hipFree(s.d_arena);
-    if (s.d_meta) (void)hipFree(s.d_meta);
-    if (s.v2.d) (void)hipFree(s.v2.d);
-    if (s.v2.h) (void)hipHostFree(s.v2.h);
-    if (s.v2.d_tops) (void)hipFree(s.v2.d_tops);
-    if (s.hy.d) (void)hipFree(s.hy.d);
-    if (s.hy.h) (void)hipHostFree(s.hy.h);
-    if (s.hy.joined) (void)hipEventDestroy(s.hy.joined);
-    free_stage(s);
-    if (s.h_meta) (void)hipHostFree(s.h_meta);
-    s = Slot{};
-    return 0;
-}
-
 int alloc_slot(Slot& s, uint64_t arena, uint32_t cap) {
     s.arena_cap = arena;
     s.cap = cap;
-    VX_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-    VX_HIP(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-    VX_HIP(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
-    if (hipMalloc(&s.d_arena, arena) != hipSuccess) return fail(VX_ENOMEM, "device arena allocation failed");
+    if (!s.stream.make(hipStreamNonBlocking) || !s.done.make(hipEventDisableTiming) ||
+        !s.copied.make(hipEventDisableTiming))
+        return fail(VX_EDEVICE, "vx_create: stream or event creation failed");
+    if (!s.d_arena.reserve(arena)) return fail(VX_ENOMEM, "device arena allocation failed");
     // The pinned stage is allocated on first use (ensure_stage): a caller that
     // registers its buffer pool never stages, and pinning slot_bytes of host
     // memory per slot up front would cost as much as the HBM arena.
     // offsets | chunk offsets | total lens | gather sources | lens | piece rows |
     // gather tile prefix (cap+1) | expected | digests | verdicts
     const size_t meta = (size_t)cap * (8 + 8 + 8 + 8 + 4 + 4 + 4 + 20 + 20 + 1) + 64;
-    if (hipHostMalloc(&s.h_meta, meta, hipHostMallocDefault) != hipSuccess)
-        return fail(VX_ENOMEM, "pinned metadata allocation failed");
-    if (hipMalloc(&s.d_meta, meta) != hipSuccess) return fail(VX_ENOMEM, "device metadata allocation failed");
+    if (!s.h_meta.reserve(meta)) return fail(VX_ENOMEM, "pinned metadata allocation failed");
+    if (!s.d_meta.reserve(meta)) return fail(VX_ENOMEM, "device metadata allocation failed");
     auto carve = [cap](uint8_t* b, uint64_t*& off, uint64_t*& poff, uint64_t*& tlen, uint64_t*& src,
                        uint32_t*& lens, uint32_t*& pidx, uint32_t*& tfirst, uint8_t*& exp, uint8_t*& dig,
                        uint8_t*& m) {
@@ -171,9 +190,9 @@ int alloc_slot(Slot& s, uint64_t arena, uint32_t cap) {
         dig = take((size_t)cap * 20);
         m = take(cap);
     };
-    carve(s.h_meta, s.h_offsets, s.h_poff, s.h_tlen, s.h_src, s.h_lens, s.h_pidx, s.h_tfirst, s.h_expected,
+    carve(s.h_meta.get(), s.h_offsets, s.h_poff, s.h_tlen, s.h_src, s.h_lens, s.h_pidx, s.h_tfirst, s.h_expected,
           s.h_digests, s.h_matched);
-    carve(s.d_meta, s.d_offsets, s.d_poff, s.d_tlen, s.d_src, s.d_lens, s.d_pidx, s.d_tfirst, s.d_expected,
+    carve(s.d_meta.get(), s.d_offsets, s.d_poff, s.d_tlen, s.d_src, s.d_lens, s.d_pidx, s.d_tfirst, s.d_expected,
           s.d_digests, s.d_matched);
     s.h_tfirst[0] = 0;
     s.tags.reserve(cap);
@@ -182,10 +201,8 @@ int alloc_slot(Slot& s, uint64_t arena, uint32_t cap) {
 
 // Pinned stage of slot s (unregistered pieces, file reads), allocated on first use.
 int ensure_stage(const vx_ctx* c, Slot& s) {
-    if (s.h_stage) return 0;
-    s.h_stage = alloc_stage(s.arena_cap, c->stage_huge != 0, &s.stage_map);
-    if (!s.h_stage && c->stage_huge) s.h_stage = alloc_stage(s.arena_cap, false, &s.stage_map);  // registration refused
-    if (!s.h_stage) return fail(VX_ENOMEM, "pinned stage allocation failed");
+    if (s.stage) return 0;
+    if (!s.stage.make(s.arena_cap, c->stage_huge != 0)) return fail(VX_ENOMEM, "pinned stage allocation failed");
     return 0;
 }
 
@@ -233,18 +250,18 @@ int warm_slots(vx_ctx* c) {
         Slot& s = c->slots[si];
         hipStream_t st = s.stream;
         if (prev >= 0) VX_HIP(hipStreamWaitEvent(st, c->slots[prev].copied, 0));
-        VX_HIP(hipMemcpyAsync(s.d_arena, s.h_meta, std::min<uint64_t>(s.arena_cap, (uint64_t)s.cap * 85),
+        VX_HIP(hipMemcpyAsync(s.d_arena.get(), s.h_meta.get(), std::min<uint64_t>(s.arena_cap, (uint64_t)s.cap * 85),
                               hipMemcpyHostToDevice, st));
         VX_HIP(hipMemcpyAsync(s.d_expected, s.h_expected, 20, hipMemcpyHostToDevice, st));
         VX_HIP(hipEventRecord(s.copied, st));
-        hipError_t e = vx::launch_uniform(s.d_arena, kAlign, 64, 1, s.d_digests, s.d_expected, s.d_matched, st,
+        hipError_t e = vx::launch_uniform(s.d_arena.get(), kAlign, 64, 1, s.d_digests, s.d_expected, s.d_matched, st,
                                           vx::kUniformDefault, nullptr);
         if (e == hipSuccess) {
             s.h_offsets[0] = 0;
             s.h_lens[0] = 64;
             VX_HIP(hipMemcpyAsync(s.d_offsets, s.h_offsets, 8, hipMemcpyHostToDevice, st));
             VX_HIP(hipMemcpyAsync(s.d_lens, s.h_lens, 4, hipMemcpyHostToDevice, st));
-            e = vx::launch_ragged(s.d_arena, s.d_offsets, s.d_lens, nullptr, 1, s.d_digests, s.d_expected,
+            e = vx::launch_ragged(s.d_arena.get(), s.d_offsets, s.d_lens, nullptr, 1, s.d_digests, s.d_expected,
                                   s.d_matched, st, vx::kUniformDefault, nullptr);
         }
         if (e != hipSuccess) return hip_fail(e, "vx_create: warm-up launch");
@@ -322,10 +339,10 @@ int batch_chunked(vx_ctx* c, const uint8_t* const* ptrs, const uint32_t* lens, c
                 s.h_tlen[r] = is_last ? Llast : L;
             }
             rc = cp.round(si, m, k > 0, false, [&](Slot& sl, hipStream_t st) {
-                if (full_rows && hipMemcpy2DAsync(sl.d_arena, dpitch, base + w0 * hs + a, hs, width, full_rows,
+                if (full_rows && hipMemcpy2DAsync(sl.d_arena.get(), dpitch, base + w0 * hs + a, hs, width, full_rows,
                                                   hipMemcpyHostToDevice, st) != hipSuccess)
                     return fail(VX_EDEVICE, "batch: chunk 2D H2D failed");
-                if (last_w && hipMemcpyAsync(sl.d_arena + full_rows * dpitch, ptrs[n - 1] + a, last_w,
+                if (last_w && hipMemcpyAsync(sl.d_arena.get() + full_rows * dpitch, ptrs[n - 1] + a, last_w,
                                              hipMemcpyHostToDevice, st) != hipSuccess)
                     return fail(VX_EDEVICE, "batch: chunk H2D failed");
                 return 0;
@@ -380,7 +397,7 @@ int batch_chunked_gather(vx_ctx* c, const uint32_t* lens, const uint8_t* expecte
                 hipMemcpyAsync(sl.d_tfirst, sl.h_tfirst, (size_t)(m + 1) * 4, hipMemcpyHostToDevice, st) !=
                     hipSuccess)
                 return fail(VX_EDEVICE, "batch: gather table H2D failed");
-            hipError_t e = vx::launch_gather(sl.d_src, sl.d_offsets, sl.d_lens, sl.d_tfirst, m, tiles, sl.d_arena, st);
+            hipError_t e = vx::launch_gather(sl.d_src, sl.d_offsets, sl.d_lens, sl.d_tfirst, m, tiles, sl.d_arena.get(), st);
             if (e != hipSuccess) return hip_fail(e, "batch: gather launch");
             c->stats.gather_tiles += tiles;
             return 0;
@@ -572,8 +589,7 @@ int vx_create(const vx_config* cfg, vx_ctx** out) {
     }
     if (!rc) rc = warm_slots(c);
     if (rc) {
-        for (auto& s : c->slots) free_slot_mem(s);
-        delete c;
+        delete c;  // every slot made so far waits for its stream and gives back what it owns
         return rc;
     }
     *out = c;
@@ -582,6 +598,9 @@ int vx_create(const vx_config* cfg, vx_ctx** out) {
 
 int vx_destroy(vx_ctx* c) {
     if (!c) return 0;
+    // The order that must hold (DESIGN.md §6 "Ownership"): the drain unless the
+    // context is sticky, the device, every stream waited for, the caller's
+    // buffers unregistered (they are not the engine's); only then the members go.
     int rc = c->sticky ? 0 : vx_drain(c, 0);
     set_device(c);
     // A failed (sticky) context skipped the drain: batches may still be
@@ -596,24 +615,8 @@ int vx_destroy(vx_ctx* c) {
     // ... and a hybrid slot's merkle work on the side stream reads its arena
     if (c->hy_stream) (void)hipStreamSynchronize(c->hy_stream);
     for (auto& r : c->registered) (void)hipHostUnregister(reinterpret_cast<void*>(r.first));
-    for (auto& s : c->slots) free_slot_mem(s);
-    if (c->d_table) (void)hipFree(c->d_table);
-    if (c->d_chunk_rows) (void)hipFree(c->d_chunk_rows);
-    for (auto& m : c->merkle) {
-        if (m.d) (void)hipFree(m.d);
-        if (m.h) (void)hipHostFree(m.h);
-    }
-    free_merkle_files(c);
-    free_holes(c);
-    if (c->mfiles.chain) (void)hipEventDestroy(c->mfiles.chain);
-    if (c->chunk_prev) (void)hipEventDestroy(c->chunk_prev);
-    for (hipEvent_t e : c->copy_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->anchor_ev) (void)hipEventDestroy(c->anchor_ev);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    if (c->hy_stream) (void)hipStreamDestroy(c->hy_stream);
-    if (c->d_hy_sha1) (void)hipFree(c->d_hy_sha1);
-    if (c->d_hy_roots) (void)hipFree(c->d_hy_roots);
+    // Everything the context owns is a handle member (a new one needs no line
+    // here); each stream among them waits once more before it is destroyed.
     delete c;
     return rc;
 }
@@ -817,12 +820,16 @@ void vx_tuning_fail_launch_after(vx_ctx* c, int64_t k) {
 void vx_tuning_verify_copy_stream(vx_ctx* c, int mode) {
     if (c) c->verify_copy_stream = mode ? 1 : 0;
 }
+void vx_tuning_live_resources(uint64_t* out) {
+    for (int k = 0; k < 4 && out; ++k) out[k] = (uint64_t)vx_res::backend::g_live[k].load();
+}
+void vx_tuning_fail_alloc_after(int64_t n) { vx_res::backend::g_fail_alloc_after = n < 0 ? -1 : n; }
 void vx_tuning_stage_huge(vx_ctx* c, int on) {
     if (!c) return;
     c->stage_huge = on ? 1 : 0;
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);  // no copy still reads a stage
     for (auto& s : c->slots)  // reallocated on next use (every slot is idle between calls)
-        if (s.state == Slot::FREE) free_stage(s);
+        if (s.state == Slot::FREE) s.stage.reset();
 }
 #endif
 int vx_tuning_plan_ragged(uint32_t n, uint32_t max_len, uint64_t total_len) {

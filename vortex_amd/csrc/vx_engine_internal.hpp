@@ -2,6 +2,8 @@
 // "Host engine"): error reporting, the slot and context structs (one layout
 // with and without VX_TEST_HOOKS), and the functions that cross units: the
 // context's primitives (vx_engine.hip) and the slot path's (vx_slots.hip).
+// Every device and pinned block, stream and event in them is a handle of
+// vx_resources.hpp; the typed pointers beside them are views into the blocks.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -35,10 +37,17 @@
 #include "vx_kernels.h"
 #include "vx_merkle_rounds.hpp"
 #include "vx_merkle_tree.hpp"
+#include "vx_resources.hpp"
 #include "vx_synth.h"
 #include "vx_tuning.h"
 
 namespace vxe {
+
+using vx_res::DeviceMem;
+using vx_res::Event;
+using vx_res::PinnedMem;
+using vx_res::Stage;
+using vx_res::Stream;
 
 // the library's one error text per thread (vx_engine.hip): fail() writes it, vx_last_error reads it
 extern thread_local std::string g_err;
@@ -70,18 +79,19 @@ struct StageCopy {
     uint32_t len;
 };
 
+// Movable (the context's vector of them), never copied.  Destroying a slot, or
+// assigning Slot{} to it, gives back all it owns: first its stream (the last
+// member), after waiting for it, then the blocks and events.
 struct Slot {
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
-    hipEvent_t copied = nullptr;  // this slot's H2D finished on the copy stream
+    Event done;
+    Event copied;  // this slot's H2D finished on the copy stream
     uint64_t arena_cap = 0;
     uint32_t cap = 0;  // pieces
-    uint8_t* d_arena = nullptr;
-    uint8_t* h_stage = nullptr;
-    uint64_t stage_map = 0;  // > 0: h_stage is a registered mmap of this many bytes (alloc_stage)
+    DeviceMem d_arena;
+    Stage stage;  // the pinned stage, made on first use (ensure_stage)
     // pinned metadata block: offsets | lens | expected | digests | matched
-    uint8_t* h_meta = nullptr;
-    uint8_t* d_meta = nullptr;
+    PinnedMem h_meta;
+    DeviceMem d_meta;
     uint64_t* h_offsets = nullptr;
     uint32_t* h_lens = nullptr;
     uint8_t* h_expected = nullptr;
@@ -111,13 +121,13 @@ struct Slot {
     // pinned block h and a device block d of expected roots (32 cap) | roots
     // (32 cap) | log2w (cap); the verdicts share h_matched / d_matched.
     struct V2 {
-        uint8_t *h = nullptr, *d = nullptr;
+        PinnedMem h;
+        DeviceMem d;
         uint8_t *h_exp32 = nullptr, *h_roots = nullptr, *h_log2w = nullptr;
         uint8_t *d_exp32 = nullptr, *d_roots = nullptr, *d_log2w = nullptr;
         // the piece kernel's work area for trees wider than 256 leaves (tile
         // tops | their log2w), grown when a launch needs more
-        uint8_t* d_tops = nullptr;
-        uint64_t tops_cap = 0;
+        DeviceMem d_tops;
         uint32_t kmax = 0;  // the widest log2w of the slot's v2 or hybrid pieces: the piece kernel runs n << kmax lanes
     } v2;
     // hybrid pieces, allocated on the slot's first hybrid use (ensure_hybrid):
@@ -126,8 +136,9 @@ struct Slot {
     // event that joins the merkle side stream.  The roots land in the v2 block.
     // rows: what the submits filled in per piece, packed at launch.
     struct Hybrid {
-        uint8_t *h = nullptr, *d = nullptr;
-        hipEvent_t joined = nullptr;
+        PinnedMem h;
+        DeviceMem d;
+        Event joined;
         struct Row {
             vx_hybrid_slot::Lane lane;
             uint8_t sha1[VX_DIGEST_LEN], root[VX_SHA256_LEN], log2w;
@@ -150,11 +161,26 @@ struct Slot {
     enum State { FREE, FILLING, INFLIGHT } state = FREE;
     uint64_t seq = 0;
     std::chrono::steady_clock::time_point t_open{};  // first piece queued (vx_stats batch latency)
+    // Declared last, so destroyed first: synchronized, then destroyed, before
+    // any block above that a queued copy or kernel may still touch is freed.
+    Stream stream;
 };
 
 }  // namespace vxe
 
+// Ownership: every resource is a handle member and goes with
+// `delete c`; a new one needs no line in vx_destroy.  Members go in reverse
+// order, so each of the context's own streams (hy_stream, copy_stream, the
+// holes') stands after the memory and the events its work uses, the slots
+// included: it is synchronized and destroyed before they are freed.  The slot
+// streams' work also uses blocks declared after the slots; every call waits
+// for it before it returns, and vx_destroy waits for every stream before the
+// members go.
 struct vx_ctx {
+    using DeviceMem = vx_res::DeviceMem;
+    using PinnedMem = vx_res::PinnedMem;
+    using Event = vx_res::Event;
+    using Stream = vx_res::Stream;
     // Everything a caller chooses comes in here (vx_config, ABI 2): the
     // engine reads no environment variables.
     vx_config cfg{};
@@ -167,11 +193,11 @@ struct vx_ctx {
     // Per-piece device rows of the chunk paths (state | expected | digest |
     // verdict), kept across calls and grown on demand: allocating them per
     // call cost ~1 ms of a 40 ms e2e batch.
-    uint8_t* d_chunk_rows = nullptr;
-    uint64_t chunk_rows_cap = 0;
-    hipEvent_t chunk_prev = nullptr;
+    DeviceMem d_chunk_rows;
+    uint64_t chunk_rows_cap = 0;  // pieces
+    Event chunk_prev;
     // Device-resident `pieces` table (vx_set_piece_table).
-    uint8_t* d_table = nullptr;
+    DeviceMem d_table;
     uint32_t n_table = 0;
     int filling = -1;
     // vx_flush found every other slot in flight and left the filling slot
@@ -185,10 +211,10 @@ struct vx_ctx {
     // table and v2 rows (vx_hybrid_set_piece_tables), and the one side stream
     // every hybrid slot's merkle work runs on, beside the slot's SHA-1 chain;
     // created on the first hybrid launch.
-    uint8_t* d_hy_sha1 = nullptr;
-    uint8_t* d_hy_roots = nullptr;
+    DeviceMem d_hy_sha1;
+    DeviceMem d_hy_roots;
     uint32_t n_hy_table = 0;
-    hipStream_t hy_stream = nullptr;
+    Stream hy_stream;
     struct Reg {
         size_t len;
         uint8_t* dev;  // device mapping of the range (hipHostGetDevicePointer)
@@ -219,7 +245,7 @@ struct vx_ctx {
     // vx_last_verify: the last file re-verify's time budget, and the timing
     // events around its chunk rounds' data copies (reused across calls)
     vx_verify_trace last_verify{};
-    std::vector<hipEvent_t> copy_ev;
+    std::vector<Event> copy_ev;
     std::vector<vx_verify_round> last_rounds;  // vx_last_verify_rounds
     // the last split call's decisions, one per round formed (vx_tuning_last_split)
     struct SplitDecision {
@@ -277,10 +303,10 @@ struct vx_ctx {
     // so no copy ever sits behind a kernel.  Created on first
     // use.  verify_copy_stream = 0 (test build only) restores the slot-stream
     // copies for A/B.
-    hipStream_t copy_stream = nullptr;
+    Stream copy_stream;
     int verify_copy_stream = 1;
-    // How pinned stages are allocated (alloc_stage): 1 = 2 MiB-aligned mmap
-    // with transparent huge pages, then hipHostRegister; 0 = hipHostMalloc
+    // How pinned stages are allocated (Stage): 1 = 2 MiB-aligned mmap with
+    // transparent huge pages, then registered; 0 = the pinned allocator
     // (vx_tuning_stage_huge, test build).  Huge pages: warm re-verify 39.1 ->
     // 45.2 GiB/s (its H2D copies 44-47 -> 49-50.5), cold 10.9 -> 14.2, median
     // of 7-9 alternating calls on one box.
@@ -293,13 +319,13 @@ struct vx_ctx {
     // 0: the slot's stage.
     int split_one_round = 1;
     uint64_t split_round_cap = 64ull << 20;
-    hipEvent_t anchor_ev = nullptr;            // maps the rounds' GPU times onto the host clock
+    Event anchor_ev;  // maps the rounds' GPU times onto the host clock
     // vx_merkle_verify_batch: per slot, a device block (metadata in | results
     // out | leaf rows) and its pinned host mirror (in | out), allocated on the
     // first call; merkle_rows = leaf rows (and pieces) one round holds.
     struct MerkleBufs {
-        uint8_t* d = nullptr;
-        uint8_t* h = nullptr;
+        DeviceMem d;
+        PinnedMem h;
     };
     std::vector<MerkleBufs> merkle;
     uint32_t merkle_rows = 0;
@@ -309,25 +335,23 @@ struct vx_ctx {
     // round's kernels after the last round's; all kept across calls and grown
     // on demand.
     struct MerkleFiles {
-        uint8_t* d_window = nullptr;
+        DeviceMem d_window;
         uint64_t window_rows = 0;
-        std::vector<uint32_t*> h_tab, d_tab;
+        std::vector<PinnedMem> h_tab;
+        std::vector<DeviceMem> d_tab;
         uint64_t tab_entries = 0;
-        uint8_t* d_call = nullptr;
+        DeviceMem d_call;
         uint64_t call_cap = 0;
-        hipEvent_t chain = nullptr;
+        Event chain;
         // ... of the calls that keep or check the leaf layer (DESIGN.md §3.7
         // "Block checks from disk"): the range's rows of the leaf table, the
         // shadow window (the stored rows where the leaf window has the data's),
         // per piece leaf_first | blocks | layer_ok, and the range's bitmap.
-        uint8_t* d_leaf = nullptr;
-        uint64_t leaf_cap = 0;  // rows
-        uint8_t* d_shadow = nullptr;
-        uint64_t shadow_rows = 0;
-        uint8_t* d_piece = nullptr;
+        DeviceMem d_leaf;
+        DeviceMem d_shadow;  // window_rows rows
+        DeviceMem d_piece;
         uint64_t piece_cap = 0;  // pieces, 9 bytes each
-        uint64_t* d_bad = nullptr;
-        uint64_t bad_cap = 0;  // words
+        DeviceMem d_bad;
     } mfiles;
     uint64_t verify_t0_ns = 0;                // the running re-verify call's start (steady clock)
     // Skipping file holes in the re-verify (vx_set_skip_holes, DESIGN.md
@@ -341,9 +365,9 @@ struct vx_ctx {
         static constexpr size_t kZeroBlock = 128, kDigestsAt = 16, kLeafAt = 64, kZeroCache = 64;
         int skip = 0;
         vx_hole_trace last{};
-        hipStream_t stream = nullptr;
-        hipEvent_t t0 = nullptr, t1 = nullptr;
-        uint8_t *h = nullptr, *d = nullptr;
+        Event t0, t1;
+        PinnedMem h;
+        DeviceMem d;
         struct Sha1Zero {
             uint32_t len;
             uint8_t digest[VX_DIGEST_LEN];
@@ -351,6 +375,7 @@ struct vx_ctx {
         std::vector<Sha1Zero> sha1_zero;
         uint8_t zero_leaf[VX_SHA256_LEN] = {};
         bool have_zero_leaf = false;
+        Stream stream;  // after its events and blocks: waited for and destroyed before they go
     } holes;
 };
 
@@ -539,7 +564,7 @@ struct BlockCall {
     }
     uint8_t* stage(size_t si, int* rc) const {
         *rc = ensure_stage(c, c->slots[si]);
-        return c->slots[si].h_stage;
+        return c->slots[si].stage.get();
     }
     // After the rounds, error or not: no copy or kernel may still use a stage.
     void sync_slots(int& rc) const {
@@ -575,10 +600,9 @@ struct BlockCall {
 // Skipping file holes (vx_reverify.hip).  ensure_holes: the zero hashes'
 // stream, events and blocks.  scan_holes: the files' extents when the setting
 // is on (else an empty set, nothing scanned), counted and timed into the
-// call's hole trace, which it resets.  free_holes: vx_destroy's part.
+// call's hole trace, which it resets.
 int ensure_holes(vx_ctx* c, const char* who);
 vx_extents::Holes scan_holes(vx_ctx* c, const std::vector<int>& fds, const uint64_t* file_lengths);
-void free_holes(vx_ctx* c);
 // vx_merkle_files.hip: the leaf row of a full unwritten block into c->holes.zero_leaf,
 // made once per context; synchronous, on the holes' stream (so before a ZeroDigests::start).
 int zero_leaf_row(vx_ctx* c, const char* who);
@@ -615,14 +639,15 @@ struct ZeroDigests {
         const int rc = ensure_holes(c, who.c_str());
         if (rc) return n = 0, rc;
         vx_ctx::Holes& h = c->holes;
-        std::memcpy(h.h, lens, sizeof(lens));
-        hipError_t e = hipMemcpyAsync(h.d, h.h, sizeof(lens), hipMemcpyHostToDevice, h.stream);
+        uint8_t *const hh = h.h.get(), *const hd = h.d.get();
+        std::memcpy(hh, lens, sizeof(lens));
+        hipError_t e = hipMemcpyAsync(hd, hh, sizeof(lens), hipMemcpyHostToDevice, h.stream);
         if (e == hipSuccess) e = hipEventRecord(h.t0, h.stream);
         if (e == hipSuccess)
-            e = vx::launch_sha1_zeros(reinterpret_cast<const uint32_t*>(h.d), (uint32_t)n, h.d + h.kDigestsAt, h.stream);
+            e = vx::launch_sha1_zeros(h.d.as<const uint32_t>(), (uint32_t)n, hd + h.kDigestsAt, h.stream);
         if (e == hipSuccess) e = hipEventRecord(h.t1, h.stream);
         if (e == hipSuccess)
-            e = hipMemcpyAsync(h.h + h.kDigestsAt, h.d + h.kDigestsAt, (size_t)n * 20, hipMemcpyDeviceToHost, h.stream);
+            e = hipMemcpyAsync(hh + h.kDigestsAt, hd + h.kDigestsAt, (size_t)n * 20, hipMemcpyDeviceToHost, h.stream);
         if (e != hipSuccess) {
             (void)hipStreamSynchronize(h.stream);
             return n = 0, hip_fail(e, (who + ": zero-piece digests").c_str());
@@ -640,14 +665,13 @@ struct ZeroDigests {
         if (hipEventElapsedTime(&ms, h.t0, h.t1) == hipSuccess) h.last.zero_hash_ms += ms;
         for (int k = 0; k < launched; ++k) {
             vx_ctx::Holes::Sha1Zero& e = have[n_have++];
-            std::memcpy(e.digest, h.h + h.kDigestsAt + (size_t)k * 20, 20);
+            std::memcpy(e.digest, h.h.get() + h.kDigestsAt + (size_t)k * 20, 20);
             if (h.sha1_zero.size() >= h.kZeroCache) h.sha1_zero.erase(h.sha1_zero.begin());
             h.sha1_zero.push_back(e);
         }
         return 0;
     }
 };
-void free_merkle_files(vx_ctx* c);  // vx_merkle_files.hip: vx_merkle_verify_files' buffers, not its event
 // vx_merkle_files.hip, the end of a v2 or hybrid hash call: the layer trees of every
 // non-empty file (vx_merkle_tree_layout) from d_rows, the whole torrent's piece
 // rows on the device in piece order, into tree_out; synchronous, on st, with a

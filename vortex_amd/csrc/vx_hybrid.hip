@@ -14,70 +14,50 @@ namespace {
 // returns (a re-verify is once per torrent; the slots and stages stay with the
 // context).
 struct HybridBufs {
-    uint8_t* d = nullptr;
-    std::vector<uint8_t*> h_tab, d_tab;
-    hipEvent_t chain = nullptr;
+    DeviceMem d;
+    std::vector<PinnedMem> h_tab;
+    std::vector<DeviceMem> d_tab;
+    Event chain;
     // The zero-tail kernel runs beside the rounds on a stream of its own (a
     // 4 MiB pad is a 65,535-block chain that nothing but the verdict waits for):
     // per slot, `state` after the round's SHA-1 kernel and `tailed` after its tails.
-    hipStream_t tail_stream = nullptr;
-    std::vector<hipEvent_t> state, tailed;
+    std::vector<Event> state, tailed;
     // The zero-run kernel of a round (file holes) runs beside
     // that round's SHA-1 kernel on a stream of its own, made when a call first
     // has a zero run: per slot, `tabled` after the round's tables are on the
     // device and `zeroed` after its zero runs.
-    hipStream_t run_stream = nullptr;
-    std::vector<hipEvent_t> tabled, zeroed;
-    ~HybridBufs() {
-        for (hipStream_t st : {tail_stream, run_stream})
-            if (st) {
-                (void)hipStreamSynchronize(st);
-                (void)hipStreamDestroy(st);
-            }
-        for (const auto* v : {&state, &tailed, &tabled, &zeroed})
-            for (hipEvent_t e : *v)
-                if (e) (void)hipEventDestroy(e);
-        if (d) (void)hipFree(d);
-        for (uint8_t* p : h_tab)
-            if (p) (void)hipHostFree(p);
-        for (uint8_t* p : d_tab)
-            if (p) (void)hipFree(p);
-        if (chain) (void)hipEventDestroy(chain);
-    }
+    std::vector<Event> tabled, zeroed;
+    // The two streams last: each is waited for and destroyed before the events
+    // and the blocks above go.
+    Stream tail_stream, run_stream;
     int make(uint64_t device_bytes, size_t nslots, uint64_t tab_bytes, const std::string& who) {
-        h_tab.assign(nslots, nullptr);
-        d_tab.assign(nslots, nullptr);
-        if (hipMalloc(&d, device_bytes) != hipSuccess) {
-            d = nullptr;
-            return fail(VX_ENOMEM, who + ": buffer allocation failed");
-        }
+        h_tab.resize(nslots);
+        d_tab.resize(nslots);
+        if (!d.reserve(device_bytes)) return fail(VX_ENOMEM, who + ": buffer allocation failed");
         for (size_t k = 0; k < nslots; ++k)
-            if (hipHostMalloc(&h_tab[k], tab_bytes, hipHostMallocDefault) != hipSuccess ||
-                hipMalloc(&d_tab[k], tab_bytes) != hipSuccess)
+            if (!h_tab[k].reserve(tab_bytes) || !d_tab[k].reserve(tab_bytes))
                 return fail(VX_ENOMEM, who + ": buffer allocation failed");
-        state.assign(nslots, nullptr);
-        tailed.assign(nslots, nullptr);
+        state.resize(nslots);
+        tailed.resize(nslots);
         // (lowest priority: the tails yield to the rounds, and HIP keeps a
         // priority's streams on hardware queues of their own, so no round's
         // kernel queues behind a long tail)
         int least = 0, greatest = 0;
-        bool ok = hipEventCreateWithFlags(&chain, hipEventDisableTiming) == hipSuccess &&
+        bool ok = chain.make(hipEventDisableTiming) &&
                   hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess &&
-                  hipStreamCreateWithPriority(&tail_stream, hipStreamNonBlocking, least) == hipSuccess;
+                  tail_stream.make_with_priority(hipStreamNonBlocking, least);
         for (size_t k = 0; k < nslots && ok; ++k)
-            ok = hipEventCreateWithFlags(&state[k], hipEventDisableTiming) == hipSuccess &&
-                 hipEventCreateWithFlags(&tailed[k], hipEventDisableTiming) == hipSuccess;
+            ok = state[k].make(hipEventDisableTiming) && tailed[k].make(hipEventDisableTiming);
         if (!ok) return fail(VX_EDEVICE, who + ": stream or event creation failed");
         return 0;
     }
     int make_run_stream(const std::string& who) {
         if (run_stream) return 0;
-        tabled.assign(state.size(), nullptr);
-        zeroed.assign(state.size(), nullptr);
-        bool ok = hipStreamCreateWithFlags(&run_stream, hipStreamNonBlocking) == hipSuccess;
+        tabled.resize(state.size());
+        zeroed.resize(state.size());
+        bool ok = run_stream.make(hipStreamNonBlocking);
         for (size_t k = 0; k < state.size() && ok; ++k)
-            ok = hipEventCreateWithFlags(&tabled[k], hipEventDisableTiming) == hipSuccess &&
-                 hipEventCreateWithFlags(&zeroed[k], hipEventDisableTiming) == hipSuccess;
+            ok = tabled[k].make(hipEventDisableTiming) && zeroed[k].make(hipEventDisableTiming);
         if (!ok) return fail(VX_EDEVICE, who + ": stream or event creation failed");
         return 0;
     }
@@ -148,9 +128,9 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
     if (c->verify_copy_stream && (rc = pipe.use_copy_stream())) return rc;
     HybridBufs hb;
     if ((rc = hb.make(o_leaves + rows * 32, c->slots.size(), tab_bytes, who))) return rc;
-    uint32_t* d_states = reinterpret_cast<uint32_t*>(hb.d);
-    uint8_t *d_exp1 = hb.d + o_exp1, *d_exp2 = hb.d + o_exp2, *d_v1 = hb.d + o_v1, *d_v2 = hb.d + o_v2;
-    uint8_t *d_lw = hb.d + o_lw, *d_leaves = hb.d + o_leaves;
+    uint32_t* d_states = hb.d.as<uint32_t>();
+    uint8_t *const hbd = hb.d.get(), *d_exp1 = hbd + o_exp1, *d_exp2 = hbd + o_exp2, *d_v1 = hbd + o_v1, *d_v2 = hbd + o_v2;
+    uint8_t *d_lw = hbd + o_lw, *d_leaves = hbd + o_leaves;
 
     if (zero_runs && (rc = hb.make_run_stream(who))) return rc;
     const bool up = hashing ||
@@ -180,7 +160,7 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
         // the round's tables in one copy: the uint64 columns, then the uint32 ones
         const size_t m = r.l_len.size(), t = r.t_len.size(), z = r.z_pid.size();
         const size_t e = r.rows.size() - r.hole_blocks;  // the block kernel's entries; the hole blocks' follow
-        uint8_t* h = hb.h_tab[si];
+        uint8_t* h = hb.h_tab[si].get();
         size_t at = 0;
         auto put = [&](const void* src, size_t bytes) {
             std::memcpy(h + at, src, bytes);
@@ -195,12 +175,12 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
         const size_t a_tpid = put(r.t_pid.data(), t * 4), a_rows = put(r.rows.data(), r.rows.size() * 4);
         const size_t a_lens = put(r.lens.data(), r.lens.size() * 4), a_zpid = put(r.z_pid.data(), z * 4);
         const size_t a_zpoff = put(r.z_poff.data(), z * 4), a_zblocks = put(r.z_blocks.data(), z * 4);
-        uint8_t* d = hb.d_tab[si];
+        uint8_t* d = hb.d_tab[si].get();
         auto u64 = [&](size_t o) { return reinterpret_cast<const uint64_t*>(d + o); };
         auto u32 = [&](size_t o) { return reinterpret_cast<const uint32_t*>(d + o); };
         hipStream_t cs = pipe.cs ? pipe.cs : s.stream;
         hipError_t err = hipSuccess;
-        if (r.bytes) err = hipMemcpyAsync(s.d_arena, s.h_stage, r.bytes, hipMemcpyHostToDevice, cs);
+        if (r.bytes) err = hipMemcpyAsync(s.d_arena.get(), s.stage.get(), r.bytes, hipMemcpyHostToDevice, cs);
         if (err == hipSuccess && pipe.cs) err = hipEventRecord(s.copied, cs);
         if (err == hipSuccess) err = hipMemcpyAsync(d, h, at, hipMemcpyHostToDevice, s.stream);
         if (err == hipSuccess && z) err = hipEventRecord(hb.tabled[si], s.stream);
@@ -219,18 +199,18 @@ int64_t hybrid_files_impl(vx_ctx* c, const char* const* paths, const uint64_t* f
             if (err == hipSuccess) err = hipEventRecord(hb.zeroed[si], hb.run_stream);
         }
         if (err == hipSuccess)
-            err = vx::launch_chunk(s.d_arena, u64(a_loff), u32(a_llen), (uint32_t)m, u32(a_lpid), u64(a_lpoff),
+            err = vx::launch_chunk(s.d_arena.get(), u64(a_loff), u32(a_llen), (uint32_t)m, u32(a_lpid), u64(a_lpoff),
                                    u64(a_ltlen), d_states, d_dig, k_exp1, k_v1, s.stream);
         if (err == hipSuccess && t) {  // the tails: after the states, beside everything else
             err = hipEventRecord(hb.state[si], s.stream);
             if (err == hipSuccess) err = hipStreamWaitEvent(hb.tail_stream, hb.state[si], 0);
             if (err == hipSuccess)
-                err = vx::launch_zero_tail(s.d_arena, u64(a_toff), u32(a_tlen), u32(a_tpad), u32(a_tpid), (uint32_t)t,
+                err = vx::launch_zero_tail(s.d_arena.get(), u64(a_toff), u32(a_tlen), u32(a_tpad), u32(a_tpid), (uint32_t)t,
                                            piece_length, d_states, d_dig, k_exp1, k_v1, hb.tail_stream);
             if (err == hipSuccess) err = hipEventRecord(hb.tailed[si], hb.tail_stream);
         }
         if (err == hipSuccess && e)
-            err = vx::launch_merkle_blocks(s.d_arena, u32(a_rows), u32(a_lens), (uint32_t)e, d_leaves, s.stream);
+            err = vx::launch_merkle_blocks(s.d_arena.get(), u32(a_rows), u32(a_lens), (uint32_t)e, d_leaves, s.stream);
         if (err == hipSuccess && r.hole_blocks)
             err = vx::launch_merkle_zero_leaves(u32(a_rows) + e, u32(a_lens) + e, r.hole_blocks, d_leaves,
                                                 c->holes.zero_leaf, s.stream);

@@ -175,22 +175,10 @@ int vx_merkle_device_root(const void* d_layer, uint32_t n, uint32_t height, void
 static int ensure_merkle(vx_ctx* c) {
     if (!c->merkle.empty()) return 0;
     const uint64_t rows = align_up(c->slots[0].arena_cap / VX_MERKLE_BLOCK, 16);
-    std::vector<vx_ctx::MerkleBufs> bufs(c->slots.size());
-    int rc = 0;
-    for (auto& m : bufs) {
-        if (hipMalloc(&m.d, rows * (48 + 48 + 32)) != hipSuccess ||
-            hipHostMalloc(&m.h, rows * (48 + 48), hipHostMallocDefault) != hipSuccess) {
-            rc = fail(VX_ENOMEM, "vx_merkle_verify_batch: buffer allocation failed");
-            break;
-        }
-    }
-    if (rc) {
-        for (auto& m : bufs) {
-            if (m.d) (void)hipFree(m.d);
-            if (m.h) (void)hipHostFree(m.h);
-        }
-        return rc;
-    }
+    std::vector<vx_ctx::MerkleBufs> bufs(c->slots.size());  // all of them, or (an early return) none
+    for (auto& m : bufs)
+        if (!m.d.reserve(rows * (48 + 48 + 32)) || !m.h.reserve(rows * (48 + 48)))
+            return fail(VX_ENOMEM, "vx_merkle_verify_batch: buffer allocation failed");
     c->merkle = std::move(bufs);
     c->merkle_rows = (uint32_t)rows;
     return 0;
@@ -237,7 +225,7 @@ int vx_merkle_verify_batch(vx_ctx* c, const uint8_t* const* ptrs, const uint32_t
         if (!r.live) return 0;
         r.live = false;
         VX_HIP(hipEventSynchronize(c->slots[si].done));
-        const uint8_t* out = c->merkle[si].h + (size_t)c->merkle_rows * 48;
+        const uint8_t* out = c->merkle[si].h.get() + (size_t)c->merkle_rows * 48;
         if (roots_out) std::memcpy(roots_out + r.first * 32, out, (size_t)r.m * 32);
         std::memcpy(matched_out + r.first, out + (size_t)r.m * 32, r.m);
         for (uint32_t k = 0; k < r.m; ++k) n_bad += matched_out[r.first + k] == 0;
@@ -250,8 +238,8 @@ int vx_merkle_verify_batch(vx_ctx* c, const uint8_t* const* ptrs, const uint32_t
         rc = harvest_round(si);  // the slot's last round: its stage and buffers are free again
         if (rc) break;
         const uint64_t R = c->merkle_rows;
-        uint8_t* h_in = c->merkle[si].h;
-        uint8_t* d_in = c->merkle[si].d;
+        uint8_t* h_in = c->merkle[si].h.get();
+        uint8_t* d_in = c->merkle[si].d.get();
         uint8_t* d_out = d_in + R * 48;
         uint8_t* d_leaves = d_in + R * 96;
         // the pieces of this round: as many as the arena and the leaf rows hold
@@ -273,7 +261,7 @@ int vx_merkle_verify_batch(vx_ctx* c, const uint8_t* const* ptrs, const uint32_t
         bool in_run = false;
         auto flush_run = [&](uint64_t hi) -> int {
             if (in_run && hi > run_lo)
-                VX_HIP(hipMemcpyAsync(s.d_arena + run_lo, s.h_stage + run_lo, hi - run_lo, hipMemcpyHostToDevice,
+                VX_HIP(hipMemcpyAsync(s.d_arena.get() + run_lo, s.stage.get() + run_lo, hi - run_lo, hipMemcpyHostToDevice,
                                       s.stream));
             in_run = false;
             return 0;
@@ -285,7 +273,7 @@ int vx_merkle_verify_batch(vx_ctx* c, const uint8_t* const* ptrs, const uint32_t
             hw[j] = log2w ? log2w[i] : (uint8_t)log2_width;
             if (lens[i] && is_registered(c, ptrs[i], lens[i])) {
                 rc = flush_run(at);
-                if (!rc && hipMemcpyAsync(s.d_arena + at, ptrs[i], lens[i], hipMemcpyHostToDevice, s.stream) !=
+                if (!rc && hipMemcpyAsync(s.d_arena.get() + at, ptrs[i], lens[i], hipMemcpyHostToDevice, s.stream) !=
                                hipSuccess)
                     rc = fail(VX_EDEVICE, "vx_merkle_verify_batch: copy from registered memory failed");
             } else if (lens[i]) {
@@ -295,7 +283,7 @@ int vx_merkle_verify_batch(vx_ctx* c, const uint8_t* const* ptrs, const uint32_t
                     in_run = true;
                     run_lo = at;
                 }
-                std::memcpy(s.h_stage + at, ptrs[i], lens[i]);
+                std::memcpy(s.stage.get() + at, ptrs[i], lens[i]);
                 c->stats.staged_bytes += lens[i];
             }
             at += align_up(lens[i], kAlign);
@@ -305,7 +293,7 @@ int vx_merkle_verify_batch(vx_ctx* c, const uint8_t* const* ptrs, const uint32_t
         if (rc) break;
         hipError_t e = hipMemcpyAsync(d_in, h_in, (size_t)m * 45, hipMemcpyHostToDevice, s.stream);
         if (e == hipSuccess)
-            e = vx::launch_merkle_ragged(s.d_arena, reinterpret_cast<const uint64_t*>(d_in + (size_t)m * 32),
+            e = vx::launch_merkle_ragged(s.d_arena.get(), reinterpret_cast<const uint64_t*>(d_in + (size_t)m * 32),
                                                 reinterpret_cast<const uint32_t*>(d_in + (size_t)m * 40),
                                                 d_in + (size_t)m * 44, m, log2_width, d_leaves, d_out, d_in,
                                                 d_out + (size_t)m * 32, s.stream);
@@ -454,23 +442,17 @@ namespace {
 // call: made per call, gone when it returns (once per torrent or per batch of
 // messages; the batch slots and their streams stay with the pieces).
 struct CallBufs {
-    hipStream_t stream = nullptr;
-    uint8_t* d = nullptr;
-    ~CallBufs() {
-        if (stream) {
-            (void)hipStreamSynchronize(stream);  // error path: no copy may still use the caller's memory
-            (void)hipStreamDestroy(stream);
-        }
-        if (d) (void)hipFree(d);
-    }
+    DeviceMem mem;
+    uint8_t* d = nullptr;  // mem's bytes
+    // After the block, so gone first and waited for: on an error path no copy
+    // may still use the block or the caller's memory.
+    Stream stream;
     int make(const vx_ctx* c, uint64_t bytes, const char* who) {
         int rc = set_device(c);
         if (rc) return rc;
-        if (hipMalloc(&d, bytes) != hipSuccess) {
-            d = nullptr;
-            return fail(VX_ENOMEM, std::string(who) + ": buffer allocation failed");
-        }
-        VX_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        if (!mem.reserve(bytes)) return fail(VX_ENOMEM, std::string(who) + ": buffer allocation failed");
+        d = mem.get();
+        if (!stream.make(hipStreamNonBlocking)) return fail(VX_EDEVICE, std::string(who) + ": stream creation failed");
         return 0;
     }
 };

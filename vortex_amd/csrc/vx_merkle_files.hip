@@ -18,24 +18,6 @@
 
 using namespace vxe;
 
-// The buffers of vx_merkle_verify_files (not its event).
-void vxe::free_merkle_files(vx_ctx* c) {
-    vx_ctx::MerkleFiles& m = c->mfiles;
-    if (m.d_window) (void)hipFree(m.d_window);
-    if (m.d_call) (void)hipFree(m.d_call);
-    if (m.d_leaf) (void)hipFree(m.d_leaf);
-    if (m.d_shadow) (void)hipFree(m.d_shadow);
-    if (m.d_piece) (void)hipFree(m.d_piece);
-    if (m.d_bad) (void)hipFree(m.d_bad);
-    for (uint32_t* p : m.h_tab)
-        if (p) (void)hipHostFree(p);
-    for (uint32_t* p : m.d_tab)
-        if (p) (void)hipFree(p);
-    hipEvent_t chain = m.chain;
-    m = vx_ctx::MerkleFiles{};
-    m.chain = chain;
-}
-
 int vxe::file_trees(vx_ctx* c, const uint8_t* d_rows, const uint64_t* file_lengths, size_t nfiles,
                     uint32_t piece_length, const std::vector<uint8_t>& bad, uint8_t* tree_out, hipStream_t st,
                     const std::string& who) {
@@ -52,9 +34,10 @@ int vxe::file_trees(vx_ctx* c, const uint8_t* d_rows, const uint64_t* file_lengt
     (void)vx_merkle::plan_trees(counts.data(), (uint32_t)counts.size(), &plan, tiles.data(), tiles.size(), off.data());
     uint32_t height = 0;
     while (((uint32_t)VX_MERKLE_BLOCK << height) < piece_length) ++height;
-    uint8_t* d = nullptr;
-    if (hipMalloc(&d, plan.tree_rows * 32 + tiles.size() * sizeof(vx_merkle_tree_tile)) != hipSuccess)
+    DeviceMem block;  // (the call waits for st before it returns, error or not)
+    if (!block.reserve(plan.tree_rows * 32 + tiles.size() * sizeof(vx_merkle_tree_tile)))
         return fail(VX_ENOMEM, who + ": tree buffer allocation failed");
+    uint8_t* const d = block.get();
     uint8_t* d_tiles = d + plan.tree_rows * 32;
     int rc = 0;
     if (hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(vx_merkle_tree_tile), hipMemcpyHostToDevice, st) !=
@@ -65,7 +48,6 @@ int vxe::file_trees(vx_ctx* c, const uint8_t* d_rows, const uint64_t* file_lengt
     if (!rc && hipMemcpyAsync(tree_out, d, plan.tree_rows * 32, hipMemcpyDeviceToHost, st) != hipSuccess)
         rc = fail(VX_EDEVICE, who + ": tree download failed");
     if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail(VX_EDEVICE, who + ": the tree passes failed");
-    (void)hipFree(d);
     if (rc) return rc;
     uint64_t piece = 0;
     for (size_t k = 0; k < counts.size(); ++k) {  // never a tree over bytes that were not read
@@ -80,52 +62,30 @@ int vxe::file_trees(vx_ctx* c, const uint8_t* d_rows, const uint64_t* file_lengt
 constexpr uint64_t kMerkleRoundCap = 64ull << 20;  // a round's stage bytes at most
 constexpr uint32_t kMerkleRunBlocks = 128;         // one pread: 2 MiB at most (32 reads for 16 readers per full round)
 
+// What vx_merkle_verify_files keeps in the context, grown on demand (a block that
+// grows is allocated anew: nothing in it outlives a call).
 static int ensure_merkle_files(vx_ctx* c, uint64_t window_rows, uint64_t entries, uint64_t count) {
     vx_ctx::MerkleFiles& m = c->mfiles;
     const char* oom = "vx_merkle_verify_files: buffer allocation failed";
-    if (!m.chain && hipEventCreateWithFlags(&m.chain, hipEventDisableTiming) != hipSuccess)
+    if (!m.chain && !m.chain.make(hipEventDisableTiming))
         return fail(VX_EDEVICE, "vx_merkle_verify_files: event creation failed");
     if (m.window_rows < window_rows) {
-        if (m.d_window) (void)hipFree(m.d_window);
-        m.d_window = nullptr;
-        m.window_rows = 0;
-        if (hipMalloc(&m.d_window, window_rows * 32) != hipSuccess) return fail(VX_ENOMEM, oom);
-        m.window_rows = window_rows;
+        m.window_rows = m.d_window.reserve(window_rows * 32) ? window_rows : 0;
+        if (!m.window_rows) return fail(VX_ENOMEM, oom);
     }
     if (m.tab_entries < entries || m.h_tab.size() != c->slots.size()) {
-        for (uint32_t* p : m.h_tab)
-            if (p) (void)hipHostFree(p);
-        for (uint32_t* p : m.d_tab)
-            if (p) (void)hipFree(p);
-        m.h_tab.assign(c->slots.size(), nullptr);
-        m.d_tab.assign(c->slots.size(), nullptr);
         m.tab_entries = 0;
+        m.h_tab.resize(c->slots.size());
+        m.d_tab.resize(c->slots.size());
         for (size_t k = 0; k < c->slots.size(); ++k)
-            if (hipHostMalloc(&m.h_tab[k], entries * 8, hipHostMallocDefault) != hipSuccess ||
-                hipMalloc(&m.d_tab[k], entries * 8) != hipSuccess)
-                return fail(VX_ENOMEM, oom);
+            if (!m.h_tab[k].reserve(entries * 8) || !m.d_tab[k].reserve(entries * 8)) return fail(VX_ENOMEM, oom);
         m.tab_entries = entries;
     }
     if (m.call_cap < count) {
-        if (m.d_call) (void)hipFree(m.d_call);
-        m.d_call = nullptr;
-        m.call_cap = 0;
         const uint64_t cap = std::max<uint64_t>(count, 4096);
-        if (hipMalloc(&m.d_call, cap * 34) != hipSuccess) return fail(VX_ENOMEM, oom);
-        m.call_cap = cap;
+        m.call_cap = m.d_call.reserve(cap * 34) ? cap : 0;
+        if (!m.call_cap) return fail(VX_ENOMEM, oom);
     }
-    return 0;
-}
-
-// A device block of at least `want` units of `unit` bytes, kept and grown like the ones above.
-template <class T>
-static int grow(T*& d, uint64_t& cap, uint64_t want, uint64_t unit, const std::string& who) {
-    if (cap >= want) return 0;
-    if (d) (void)hipFree(d);
-    d = nullptr;
-    cap = 0;
-    if (hipMalloc(&d, want * unit) != hipSuccess) return fail(VX_ENOMEM, who + ": leaf-table buffer allocation failed");
-    cap = want;
     return 0;
 }
 
@@ -151,20 +111,21 @@ int vxe::zero_leaf_row(vx_ctx* c, const char* who) {
     int rc = ensure_holes(c, who);
     if (rc) return rc;
     const uint32_t len = VX_MERKLE_BLOCK;
-    std::memcpy(h.h, &len, sizeof(len));
-    hipError_t e = hipMemcpyAsync(h.d, h.h, sizeof(len), hipMemcpyHostToDevice, h.stream);
+    uint8_t *const hh = h.h.get(), *const hd = h.d.get();
+    std::memcpy(hh, &len, sizeof(len));
+    hipError_t e = hipMemcpyAsync(hd, hh, sizeof(len), hipMemcpyHostToDevice, h.stream);
     if (e == hipSuccess) e = hipEventRecord(h.t0, h.stream);
     if (e == hipSuccess)
-        e = vx::launch_merkle_zero_leaves(nullptr, reinterpret_cast<const uint32_t*>(h.d), 1, h.d + h.kLeafAt, nullptr,
+        e = vx::launch_merkle_zero_leaves(nullptr, h.d.as<const uint32_t>(), 1, hd + h.kLeafAt, nullptr,
                                           h.stream);
     if (e == hipSuccess) e = hipEventRecord(h.t1, h.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h.h + h.kLeafAt, h.d + h.kLeafAt, 32, hipMemcpyDeviceToHost, h.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hh + h.kLeafAt, hd + h.kLeafAt, 32, hipMemcpyDeviceToHost, h.stream);
     const hipError_t sync = hipStreamSynchronize(h.stream);
     if (e != hipSuccess || sync != hipSuccess)
         return hip_fail(e != hipSuccess ? e : sync, (std::string(who) + ": zero leaf row").c_str());
     float ms = 0;
     if (hipEventElapsedTime(&ms, h.t0, h.t1) == hipSuccess) h.last.zero_hash_ms += ms;
-    std::memcpy(h.zero_leaf, h.h + h.kLeafAt, 32);
+    std::memcpy(h.zero_leaf, hh + h.kLeafAt, 32);
     h.have_zero_leaf = true;
     return 0;
 }
@@ -205,21 +166,24 @@ static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint
     const uint32_t entries = 2 * bpr + piece_length / VX_MERKLE_BLOCK;
     if ((rc = ensure_merkle_files(c, R, entries, count))) return rc;
     vx_ctx::MerkleFiles& mf = c->mfiles;
-    uint8_t *d_exp = mf.d_call, *d_match = d_exp + mf.call_cap * 32, *d_lw = d_exp + mf.call_cap * 33;
+    uint8_t *d_exp = mf.d_call.get(), *d_match = d_exp + mf.call_cap * 32, *d_lw = d_exp + mf.call_cap * 33;
     // The leaf table's part: the range's rows (uploaded here as d_exp is, or
     // downloaded after the last round), leaf_first | blocks | layer_ok per
     // piece, and when checking the shadow window and the bitmap, cleared once:
     // a group narrower than the call writes only the words it covers.
     const uint64_t words = (uint64_t)count * wpp;
-    if (lt && ((rc = grow(mf.d_leaf, mf.leaf_cap, lr.rows, 32, who)) ||
-               (rc = grow(mf.d_piece, mf.piece_cap, std::max<uint64_t>(count, 4096), 9, who))))
-        return rc;
-    if (checking && ((rc = grow(mf.d_shadow, mf.shadow_rows, mf.window_rows, 32, who)) ||
-                     (rc = grow(mf.d_bad, mf.bad_cap, words, 8, who))))
-        return rc;
-    uint32_t* d_first = reinterpret_cast<uint32_t*>(mf.d_piece);
+    if (lt && mf.piece_cap < count) {
+        const uint64_t cap = std::max<uint64_t>(count, 4096);
+        mf.piece_cap = mf.d_piece.reserve(cap * 9) ? cap : 0;
+    }
+    if ((lt && (!mf.piece_cap || !mf.d_leaf.reserve(lr.rows * 32))) ||
+        (checking && (!mf.d_shadow.reserve(mf.window_rows * 32) || !mf.d_bad.reserve(words * 8))))
+        return fail(VX_ENOMEM, who + ": leaf-table buffer allocation failed");
+    uint8_t *const d_window = mf.d_window.get(), *const d_leaf = mf.d_leaf.get(), *const d_shadow = mf.d_shadow.get();
+    uint64_t* const d_bad = mf.d_bad.as<uint64_t>();
+    uint32_t* d_first = mf.d_piece.as<uint32_t>();
     uint32_t* d_blocks = d_first + mf.piece_cap;
-    uint8_t* d_layer_ok = mf.d_piece + mf.piece_cap * 8;
+    uint8_t* d_layer_ok = mf.d_piece.get() + mf.piece_cap * 8;
 
     BlockCall call{c, who, first, count};
     bool up = hashing || hipMemcpy(d_exp, expected + 32 * first, count * 32, hipMemcpyHostToDevice) == hipSuccess;
@@ -227,9 +191,9 @@ static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint
         up = up && hipMemcpy(d_first, lr.leaf_first.data(), count * 4, hipMemcpyHostToDevice) == hipSuccess &&
              hipMemcpy(d_blocks, lr.blocks.data(), count * 4, hipMemcpyHostToDevice) == hipSuccess;
     if (checking)  // (call.begin waits for the null stream)
-        up = up && hipMemcpy(mf.d_leaf, lt->expected_leaves + lr.base * 32, lr.rows * 32, hipMemcpyHostToDevice) ==
+        up = up && hipMemcpy(d_leaf, lt->expected_leaves + lr.base * 32, lr.rows * 32, hipMemcpyHostToDevice) ==
                        hipSuccess &&
-             hipMemsetAsync(mf.d_bad, 0, words * 8, nullptr) == hipSuccess &&
+             hipMemsetAsync(d_bad, 0, words * 8, nullptr) == hipSuccess &&
              hipMemsetAsync(d_layer_ok, 0, count, nullptr) == hipSuccess;
     if ((rc = call.begin(up, paths, file_lengths, nfiles, piece_length, d_lw, d_match, count, matched_out))) return rc;
     // Blocks that lie wholly in file holes are not read: the
@@ -247,34 +211,34 @@ static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint
         Slot& s = c->slots[si];
         // the tables: rows | lens, each the block kernel's m entries, then the hole blocks'
         const uint32_t all = (uint32_t)r.rows.size(), m = all - r.hole_blocks;
-        uint32_t *h_tab = mf.h_tab[si], *d_tab = mf.d_tab[si];
+        uint32_t *h_tab = mf.h_tab[si].as<uint32_t>(), *d_tab = mf.d_tab[si].as<uint32_t>();
         std::memcpy(h_tab, r.rows.data(), (size_t)all * 4);
         std::memcpy(h_tab + all, r.lens.data(), (size_t)all * 4);
         hipError_t e = hipSuccess;
-        if (r.bytes) e = hipMemcpyAsync(s.d_arena, s.h_stage, r.bytes, hipMemcpyHostToDevice, s.stream);
+        if (r.bytes) e = hipMemcpyAsync(s.d_arena.get(), s.stage.get(), r.bytes, hipMemcpyHostToDevice, s.stream);
         if (e == hipSuccess) e = hipMemcpyAsync(d_tab, h_tab, (size_t)all * 8, hipMemcpyHostToDevice, s.stream);
         if (e == hipSuccess && call.totals.rounds) e = hipStreamWaitEvent(s.stream, mf.chain, 0);
         if (const int injected = e == hipSuccess ? injected_launch_failure(c, who) : 0) return injected;
         if (e == hipSuccess && m)
-            e = vx::launch_merkle_blocks(s.d_arena, d_tab, d_tab + all, m, mf.d_window, s.stream);
+            e = vx::launch_merkle_blocks(s.d_arena.get(), d_tab, d_tab + all, m, d_window, s.stream);
         if (e == hipSuccess && r.hole_blocks)
-            e = vx::launch_merkle_zero_leaves(d_tab + m, d_tab + all + m, r.hole_blocks, mf.d_window,
+            e = vx::launch_merkle_zero_leaves(d_tab + m, d_tab + all + m, r.hole_blocks, d_window,
                                               c->holes.zero_leaf, s.stream);
         for (const vx_merkle::Nodes& g : r.nodes) {
             if (e != hipSuccess) break;
             const uint64_t k = g.first - first;
-            e = vx::launch_merkle_nodes(mf.d_window + (size_t)g.row0 * 32, d_lw + k, g.n, g.log2_width,
+            e = vx::launch_merkle_nodes(d_window + (size_t)g.row0 * 32, d_lw + k, g.n, g.log2_width,
                                         hashing ? d_exp + k * 32 : nullptr, hashing ? nullptr : d_exp + k * 32,
                                         hashing ? nullptr : d_match + k, s.stream);
             if (!lt || e != hipSuccess) continue;
             // the group's leaf rows out to the table, or against it: the bits, and the stored
             // rows into the shadow window, which must reduce to the same expected rows
-            e = vx::launch_merkle_leaf_check(mf.d_window, g.row0, g.n, g.log2_width, wpp, d_first + k, d_blocks + k,
-                                             checking ? mf.d_leaf : nullptr, checking ? mf.d_bad + k * wpp : nullptr,
-                                             checking ? mf.d_shadow : nullptr, checking ? nullptr : mf.d_leaf,
+            e = vx::launch_merkle_leaf_check(d_window, g.row0, g.n, g.log2_width, wpp, d_first + k, d_blocks + k,
+                                             checking ? d_leaf : nullptr, checking ? d_bad + k * wpp : nullptr,
+                                             checking ? d_shadow : nullptr, checking ? nullptr : d_leaf,
                                              s.stream);
             if (checking && e == hipSuccess)
-                e = vx::launch_merkle_nodes(mf.d_shadow + (size_t)g.row0 * 32, d_lw + k, g.n, g.log2_width, nullptr,
+                e = vx::launch_merkle_nodes(d_shadow + (size_t)g.row0 * 32, d_lw + k, g.n, g.log2_width, nullptr,
                                             d_exp + k * 32, d_layer_ok + k, s.stream);
         }
         if (e == hipSuccess) e = hipEventRecord(mf.chain, s.stream);
@@ -297,11 +261,11 @@ static int64_t merkle_files_impl(vx_ctx* c, const char* const* paths, const uint
     if (!rc && tree_out)  // (the whole torrent: first == 0, count == n_pieces)
         rc = file_trees(c, d_exp, file_lengths, nfiles, piece_length, call.bad, tree_out, c->slots[0].stream, who);
     uint8_t* const leaves = lt && hashing ? lt->leaves_out + lr.base * 32 : nullptr;  // the range's rows
-    if (!rc && leaves && hipMemcpy(leaves, mf.d_leaf, lr.rows * 32, hipMemcpyDeviceToHost) != hipSuccess)
+    if (!rc && leaves && hipMemcpy(leaves, d_leaf, lr.rows * 32, hipMemcpyDeviceToHost) != hipSuccess)
         rc = fail(VX_EDEVICE, who + ": leaf table download failed");
     std::vector<uint8_t> layer_ok(checking ? count : 0);
     if (!rc && checking &&
-        (hipMemcpy(lt->bad_out, mf.d_bad, words * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+        (hipMemcpy(lt->bad_out, d_bad, words * 8, hipMemcpyDeviceToHost) != hipSuccess ||
          hipMemcpy(layer_ok.data(), d_layer_ok, count, hipMemcpyDeviceToHost) != hipSuccess))
         rc = fail(VX_EDEVICE, who + ": bitmap download failed");
     call.trace((uint64_t)bpr * VX_MERKLE_BLOCK);

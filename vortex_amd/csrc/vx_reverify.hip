@@ -89,7 +89,7 @@ int verify_whole(FileVerify& fv, vx_files::Readers& rd, uint64_t n, uint32_t pl,
                 const uint64_t i = todo[t];
                 const uint32_t len = (uint32_t)(i == n - 1 ? last_len : pl);
                 const uint32_t k = (uint32_t)(t - lo);
-                runs.add(it, s.h_stage + k * stride, i, len);
+                runs.add(it, s.stage.get() + k * stride, i, len);
                 s.h_offsets[k] = k * stride;
                 s.h_lens[k] = len;
                 if (len != s.h_lens[0]) s.uniform = false;
@@ -184,7 +184,7 @@ int verify_chunked(FileVerify& fv, vx_files::Readers& rd, uint64_t n, uint32_t p
             const uint64_t len_i = i == n - 1 ? last_len : pl;
             if (r.a >= len_i && !(r.a == 0 && len_i == 0)) continue;  // piece already finished
             const uint64_t clen = std::min<uint64_t>(r.len, len_i - r.a);
-            it.push_back(vx_files::ReadItem{s.h_stage + (uint64_t)m * pitch, i, r.a, clen});
+            it.push_back(vx_files::ReadItem{s.stage.get() + (uint64_t)m * pitch, i, r.a, clen});
             s.h_offsets[m] = (uint64_t)m * pitch;
             s.h_lens[m] = (uint32_t)clen;
             s.h_pidx[m] = (uint32_t)(i - first);
@@ -229,32 +229,13 @@ namespace vxe {
 
 int ensure_holes(vx_ctx* c, const char* who) {
     vx_ctx::Holes& h = c->holes;
-    if (h.stream) return 0;  // made together
-    hipStream_t st = nullptr;
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess)
+    if (h.d) return 0;  // made together, this one last
+    if (!h.stream && !h.stream.make(hipStreamNonBlocking))
         return fail(VX_EDEVICE, std::string(who) + ": stream creation failed");
-    if (hipEventCreate(&h.t0) != hipSuccess || hipEventCreate(&h.t1) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&h.h), h.kZeroBlock, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&h.d), h.kZeroBlock) != hipSuccess) {
-        h.stream = st;
-        free_holes(c);
+    if ((!h.t0 && !h.t0.make(hipEventDefault)) || (!h.t1 && !h.t1.make(hipEventDefault)) ||  // (timed)
+        !h.h.reserve(h.kZeroBlock) || !h.d.reserve(h.kZeroBlock))
         return fail(VX_ENOMEM, std::string(who) + ": zero-hash buffers");
-    }
-    h.stream = st;
     return 0;
-}
-
-void free_holes(vx_ctx* c) {
-    vx_ctx::Holes& h = c->holes;
-    if (h.stream) (void)hipStreamSynchronize(h.stream);
-    if (h.t0) (void)hipEventDestroy(h.t0);
-    if (h.t1) (void)hipEventDestroy(h.t1);
-    if (h.h) (void)hipHostFree(h.h);
-    if (h.d) (void)hipFree(h.d);
-    if (h.stream) (void)hipStreamDestroy(h.stream);
-    h.t0 = h.t1 = nullptr;
-    h.h = h.d = nullptr;
-    h.stream = nullptr;
 }
 
 vx_extents::Holes scan_holes(vx_ctx* c, const std::vector<int>& fds, const uint64_t* file_lengths) {

@@ -7,7 +7,7 @@
 //    (place), the kind's expected rows (record_rows), commit and launch;
 //  * launch_slot_impl: one enqueue sequence per kind (launch_v1, launch_v2,
 //    launch_hybrid) over the steps they share (copy_runs, gather_into_arena,
-//    grow_tops, mark_inflight);
+//    mark_inflight);
 //  * harvest / reap / poll_impl: results back, per kind.
 // The file re-verify (vx_reverify.hip) fills slots by hand and launches them
 // as v1 slots through launch_slot; the chunk rounds (vx_chunk_pipe.hpp) use
@@ -24,15 +24,11 @@ constexpr uint32_t kZcMinPieces = 128;
 // The v2 buffers of slot s (vx_merkle_submit), allocated on its first v2 piece:
 // a context that only sees v1 pieces allocates nothing for v2.
 static int ensure_v2(Slot& s) {
-    if (s.v2.h) return 0;
+    if (s.v2.d) return 0;  // (made last)
     const size_t bytes = (size_t)s.cap * (32 + 32 + 1) + 64;
-    uint8_t *h = nullptr, *d = nullptr;
-    if (hipHostMalloc(&h, bytes, hipHostMallocDefault) != hipSuccess || hipMalloc(&d, bytes) != hipSuccess) {
-        if (h) (void)hipHostFree(h);
+    if (!s.v2.h.reserve(bytes) || !s.v2.d.reserve(bytes))
         return fail(VX_ENOMEM, "vx_merkle_submit: v2 metadata allocation failed");
-    }
-    s.v2.h = s.v2.h_exp32 = h;
-    s.v2.d = s.v2.d_exp32 = d;
+    uint8_t *const h = s.v2.h_exp32 = s.v2.h.get(), *const d = s.v2.d_exp32 = s.v2.d.get();
     s.v2.h_roots = h + (size_t)s.cap * 32;
     s.v2.h_log2w = h + (size_t)s.cap * 64;
     s.v2.d_roots = d + (size_t)s.cap * 32;
@@ -44,19 +40,10 @@ static int ensure_v2(Slot& s) {
 // hybrid piece, beside the v2 block that takes the roots.
 static int ensure_hybrid(Slot& s) {
     if (int rc = ensure_v2(s)) return rc;
-    if (s.hy.h) return 0;
+    if (s.hy.joined) return 0;  // (made last)
     const size_t bytes = vx_hybrid_slot::pack(s.cap).bytes;
-    uint8_t *h = nullptr, *d = nullptr;
-    hipEvent_t ev = nullptr;
-    if (hipHostMalloc(&h, bytes, hipHostMallocDefault) != hipSuccess || hipMalloc(&d, bytes) != hipSuccess ||
-        hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-        if (h) (void)hipHostFree(h);
-        if (d) (void)hipFree(d);
+    if (!s.hy.h.reserve(bytes) || !s.hy.d.reserve(bytes) || !s.hy.joined.make(hipEventDisableTiming))
         return fail(VX_ENOMEM, "vx_hybrid_submit: hybrid metadata allocation failed");
-    }
-    s.hy.h = h;
-    s.hy.d = d;
-    s.hy.joined = ev;
     return 0;
 }
 
@@ -73,7 +60,7 @@ static void stage_copies(Slot& s) {
     static const unsigned hw = usable_cpus();
     const unsigned T = (unsigned)std::min<uint64_t>({16, hw, std::max<uint64_t>(1, s.staged_bytes / per)});
     auto copy = [&s](size_t a, size_t b) {
-        for (size_t k = a; k < b; ++k) std::memcpy(s.h_stage + s.staged[k].off, s.staged[k].src, s.staged[k].len);
+        for (size_t k = a; k < b; ++k) std::memcpy(s.stage.get() + s.staged[k].off, s.staged[k].src, s.staged[k].len);
     };
     if (T <= 1) copy(0, s.staged.size());
     else {
@@ -141,9 +128,9 @@ bool zc_loader_wins(uint32_t n) { return n < kZcMinPieces; }
 // The slot's direct runs, then its staged runs, into the arena.
 static int copy_runs(Slot& s, hipStream_t cs) {
     for (const DirectRun& r : s.druns)
-        VX_HIP(hipMemcpyAsync(s.d_arena + r.lo, r.host, r.hi - r.lo, hipMemcpyHostToDevice, cs));
+        VX_HIP(hipMemcpyAsync(s.d_arena.get() + r.lo, r.host, r.hi - r.lo, hipMemcpyHostToDevice, cs));
     for (const Run& r : s.runs)
-        VX_HIP(hipMemcpyAsync(s.d_arena + r.lo, s.h_stage + r.lo, r.hi - r.lo, hipMemcpyHostToDevice, cs));
+        VX_HIP(hipMemcpyAsync(s.d_arena.get() + r.lo, s.stage.get() + r.lo, r.hi - r.lo, hipMemcpyHostToDevice, cs));
     return 0;
 }
 
@@ -157,7 +144,7 @@ static int gather_into_arena(vx_ctx* c, Slot& s, const uint64_t* d_src, const ui
     // With shorter pieces the hash kernels compete and 128 cost up to 10 %
     // (1 MiB: -2 %).
     const uint32_t grid = s.bytes >= (uint64_t)s.n << 21 ? 128u : 0u;
-    hipError_t e = vx::launch_gather(d_src, d_offsets, d_lens, d_tfirst, s.n, s.gtiles, s.d_arena, cs, grid);
+    hipError_t e = vx::launch_gather(d_src, d_offsets, d_lens, d_tfirst, s.n, s.gtiles, s.d_arena.get(), cs, grid);
     if (e != hipSuccess) return hip_fail(e, "gather launch");
     c->stats.gather_tiles += s.gtiles;
     return 0;
@@ -179,17 +166,6 @@ static int copy_pieces(vx_ctx* c, int si, bool tables) {
     VX_HIP(hipMemcpyAsync(s.d_src, s.h_src, (size_t)s.n * 8, hipMemcpyHostToDevice, cs));
     VX_HIP(hipMemcpyAsync(s.d_tfirst, s.h_tfirst, (size_t)(s.n + 1) * 4, hipMemcpyHostToDevice, cs));
     return gather_into_arena(c, s, s.d_src, s.d_offsets, s.d_lens, s.d_tfirst, cs);
-}
-
-// The merkle piece kernel's work area holds `need` bytes, or `none`.
-static int grow_tops(Slot::V2& v, uint64_t need, const char* none) {
-    if (need <= v.tops_cap) return 0;
-    if (v.d_tops) (void)hipFree(v.d_tops);
-    v.d_tops = nullptr;
-    v.tops_cap = 0;
-    if (hipMalloc(&v.d_tops, need) != hipSuccess) return fail(VX_ENOMEM, none);
-    v.tops_cap = need;
-    return 0;
 }
 
 // The end of every launch: the verdict column back, `done` behind it.
@@ -224,7 +200,7 @@ static int launch_v1(vx_ctx* c, int si) {
         VX_HIP(hipMemcpyAsync(s.d_pidx, s.h_pidx, (size_t)n * 4, hipMemcpyHostToDevice, cs));
     else if (s.has_expected)
         VX_HIP(hipMemcpyAsync(s.d_expected, s.h_expected, (size_t)n * 20, hipMemcpyHostToDevice, cs));
-    const uint8_t* d_exp = s.use_table ? c->d_table : (s.has_expected ? s.d_expected : nullptr);
+    const uint8_t* d_exp = s.use_table ? c->d_table.get() : (s.has_expected ? s.d_expected : nullptr);
     const uint32_t* d_row = s.use_table ? s.d_pidx : nullptr;
     VX_HIP(hipEventRecord(s.copied, cs));
     mark_launched(c, si);
@@ -237,7 +213,7 @@ static int launch_v1(vx_ctx* c, int si) {
     } else if (s.uniform) {
         const uint32_t len = s.h_lens[0];
         const uint64_t stride = align_up(std::max<uint32_t>(len, 1), kAlign);
-        e = vx::launch_uniform(s.d_arena, stride, len, n, s.d_digests, d_exp, s.d_matched, cs, vx::kUniformDefault,
+        e = vx::launch_uniform(s.d_arena.get(), stride, len, n, s.d_digests, d_exp, s.d_matched, cs, vx::kUniformDefault,
                                d_row);
     } else {
         uint64_t max_len = 0, total = 0;
@@ -245,7 +221,7 @@ static int launch_v1(vx_ctx* c, int si) {
             max_len = std::max<uint64_t>(max_len, s.h_lens[i]);
             total += s.h_lens[i];
         }
-        e = vx::launch_ragged(s.d_arena, s.d_offsets, s.d_lens, nullptr, n, s.d_digests, d_exp, s.d_matched, cs,
+        e = vx::launch_ragged(s.d_arena.get(), s.d_offsets, s.d_lens, nullptr, n, s.d_digests, d_exp, s.d_matched, cs,
                               vx::plan_ragged(n, max_len, total), d_row);
     }
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
@@ -270,12 +246,12 @@ static int launch_v2(vx_ctx* c, int si) {
     mark_launched(c, si);
     uint8_t *d_exp = s.has_expected ? v.d_exp32 : nullptr, *d_matched = s.has_expected ? s.d_matched : nullptr;
 #if VX_MERKLE_ASYNC_FUSED
-    if (int rc = grow_tops(s.v2, vx::merkle_pieces_work(n, K), "v2 tile tops allocation failed")) return rc;
-    hipError_t e = vx::launch_merkle_pieces(s.d_arena, s.d_offsets, s.d_lens, v.d_log2w, n, K, v.d_tops, v.d_roots,
+    if (!v.d_tops.reserve(vx::merkle_pieces_work(n, K))) return fail(VX_ENOMEM, "v2 tile tops allocation failed");
+    hipError_t e = vx::launch_merkle_pieces(s.d_arena.get(), s.d_offsets, s.d_lens, v.d_log2w, n, K, v.d_tops.get(), v.d_roots,
                                             d_exp, d_matched, cs);
 #else  // the A/B leg (vx_tuning.h): the leaf + node pair, d_tops its leaf array
-    if (int rc = grow_tops(s.v2, ((uint64_t)n << K) * 32, "v2 tile tops allocation failed")) return rc;
-    hipError_t e = vx::launch_merkle_ragged(s.d_arena, s.d_offsets, s.d_lens, v.d_log2w, n, K, v.d_tops, v.d_roots,
+    if (!v.d_tops.reserve(((uint64_t)n << K) * 32)) return fail(VX_ENOMEM, "v2 tile tops allocation failed");
+    hipError_t e = vx::launch_merkle_ragged(s.d_arena.get(), s.d_offsets, s.d_lens, v.d_log2w, n, K, v.d_tops.get(), v.d_roots,
                                             d_exp, d_matched, cs);
 #endif
     if (e != hipSuccess) return hip_fail(e, "merkle piece kernel launch");
@@ -308,12 +284,14 @@ static int launch_hybrid(vx_ctx* c, int si) {
         // 3 ms chain (profiles/hybrid/async.json, "side_stream").
         int least = 0, greatest = 0;
         VX_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        VX_HIP(hipStreamCreateWithPriority(&c->hy_stream, hipStreamNonBlocking, greatest));
+        if (!c->hy_stream.make_with_priority(hipStreamNonBlocking, greatest))
+            return fail(VX_EDEVICE, "hybrid launch: side stream creation failed");
     }
-    if (int rc = grow_tops(s.v2, vx::merkle_pieces_work(n, K), "hybrid tile tops allocation failed")) return rc;
+    if (!s.v2.d_tops.reserve(vx::merkle_pieces_work(n, K)))
+        return fail(VX_ENOMEM, "hybrid tile tops allocation failed");
     // pack what the submits filled in (vx_hybrid_slot::Pack)
     const vx_hybrid_slot::Pack p = vx_hybrid_slot::pack(n);
-    uint8_t *h = hy.h, *d = hy.d;
+    uint8_t *h = hy.h.get(), *d = hy.d.get();
     auto h64 = [&](size_t o) { return reinterpret_cast<uint64_t*>(h + o); };
     auto h32 = [&](size_t o) { return reinterpret_cast<uint32_t*>(h + o); };
     std::memcpy(h + p.offsets, s.h_offsets, (size_t)n * 8);
@@ -346,19 +324,19 @@ static int launch_hybrid(vx_ctx* c, int si) {
     mark_launched(c, si);
     // the merkle side, beside the chain
     VX_HIP(hipStreamWaitEvent(c->hy_stream, s.copied, 0));
-    hipError_t e = vx::launch_merkle_pieces(s.d_arena, d64(p.offsets), d32(p.lens), d + p.log2w, n, K, s.v2.d_tops,
+    hipError_t e = vx::launch_merkle_pieces(s.d_arena.get(), d64(p.offsets), d32(p.lens), d + p.log2w, n, K, s.v2.d_tops.get(),
                                             s.v2.d_roots, nullptr, nullptr, c->hy_stream);
     if (e != hipSuccess) return hip_fail(e, "hybrid merkle piece kernel launch");
     VX_HIP(hipEventRecord(hy.joined, c->hy_stream));
     // the SHA-1 side: whole data blocks, then the join and the finish kernel
     uint32_t* d_states = d32(p.states);
-    e = vx::launch_chunk(s.d_arena, d64(p.offsets), d32(p.chunks), n, d32(p.ident), d64(p.poffs), d64(p.totals),
+    e = vx::launch_chunk(s.d_arena.get(), d64(p.offsets), d32(p.chunks), n, d32(p.ident), d64(p.poffs), d64(p.totals),
                          d_states, s.d_digests, nullptr, nullptr, cs);
     if (e != hipSuccess) return hip_fail(e, "hybrid chunk kernel launch");
     VX_HIP(hipStreamWaitEvent(cs, hy.joined, 0));
-    const uint8_t* exp1 = s.use_table ? c->d_hy_sha1 : d + p.exp_sha1;
-    const uint8_t* exp2 = s.use_table ? c->d_hy_roots : d + p.exp_roots;
-    e = vx::launch_hybrid_finish(s.d_arena, d64(p.tail_offs), d32(p.lens), d32(p.pads), n, hy.total ? hy.total : 64,
+    const uint8_t* exp1 = s.use_table ? c->d_hy_sha1.get() : d + p.exp_sha1;
+    const uint8_t* exp2 = s.use_table ? c->d_hy_roots.get() : d + p.exp_roots;
+    e = vx::launch_hybrid_finish(s.d_arena.get(), d64(p.tail_offs), d32(p.lens), d32(p.pads), n, hy.total ? hy.total : 64,
                                  d_states, s.d_digests, s.v2.d_roots, exp1, exp2, s.use_table ? d32(p.rows) : nullptr,
                                  d + p.flags, s.d_matched, cs);
     if (e != hipSuccess) return hip_fail(e, "hybrid finish kernel launch");
@@ -588,7 +566,7 @@ static int place(vx_ctx* c, Slot& s, const uint8_t* data, uint32_t len, uint64_t
                 s.staged.push_back(StageCopy{data, off, len});
                 s.staged_bytes += len;
             } else {
-                std::memcpy(s.h_stage + off, data, len);
+                std::memcpy(s.stage.get() + off, data, len);
             }
             if (!s.runs.empty() && align_up(s.runs.back().hi, kAlign) == off)
                 s.runs.back().hi = off + len;  // (off is aligned) the alignment gap travels too
@@ -735,13 +713,12 @@ int vx_set_piece_table(vx_ctx* c, const uint8_t* table, uint32_t n_pieces) {
     if (!c || (n_pieces && !table)) return fail(VX_EINVAL, "vx_set_piece_table: bad argument");
     if (c->pending || c->filling >= 0) return fail(VX_EBUSY, "vx_set_piece_table: pieces in flight");
     if (int rc = set_device(c)) return rc;
-    if (c->d_table) (void)hipFree(c->d_table);
-    c->d_table = nullptr;
+    c->d_table.reset();
     c->n_table = 0;
     if (!n_pieces) return 0;
-    if (hipMalloc(&c->d_table, (size_t)n_pieces * 20) != hipSuccess)
+    if (!c->d_table.reserve((size_t)n_pieces * 20))
         return fail(VX_ENOMEM, "vx_set_piece_table: device allocation failed");
-    VX_HIP(hipMemcpy(c->d_table, table, (size_t)n_pieces * 20, hipMemcpyHostToDevice));
+    VX_HIP(hipMemcpy(c->d_table.get(), table, (size_t)n_pieces * 20, hipMemcpyHostToDevice));
     c->n_table = n_pieces;
     return 0;
 }
@@ -817,19 +794,14 @@ int vx_hybrid_set_piece_tables(vx_ctx* c, const uint8_t* sha1_table, const uint8
         return fail(VX_EINVAL, "vx_hybrid_set_piece_tables: bad argument");
     if (c->pending || c->filling >= 0) return fail(VX_EBUSY, "vx_hybrid_set_piece_tables: pieces in flight");
     if (int rc = set_device(c)) return rc;
-    if (c->d_hy_sha1) (void)hipFree(c->d_hy_sha1);
-    if (c->d_hy_roots) (void)hipFree(c->d_hy_roots);
-    c->d_hy_sha1 = c->d_hy_roots = nullptr;
+    c->d_hy_sha1.reset();
+    c->d_hy_roots.reset();
     c->n_hy_table = 0;
     if (!n_pieces) return 0;
-    if (hipMalloc(&c->d_hy_sha1, (size_t)n_pieces * 20) != hipSuccess ||
-        hipMalloc(&c->d_hy_roots, (size_t)n_pieces * 32) != hipSuccess) {
-        if (c->d_hy_sha1) (void)hipFree(c->d_hy_sha1);
-        c->d_hy_sha1 = c->d_hy_roots = nullptr;
+    if (!c->d_hy_sha1.reserve((size_t)n_pieces * 20) || !c->d_hy_roots.reserve((size_t)n_pieces * 32))
         return fail(VX_ENOMEM, "vx_hybrid_set_piece_tables: device allocation failed");
-    }
-    VX_HIP(hipMemcpy(c->d_hy_sha1, sha1_table, (size_t)n_pieces * 20, hipMemcpyHostToDevice));
-    VX_HIP(hipMemcpy(c->d_hy_roots, roots_table, (size_t)n_pieces * 32, hipMemcpyHostToDevice));
+    VX_HIP(hipMemcpy(c->d_hy_sha1.get(), sha1_table, (size_t)n_pieces * 20, hipMemcpyHostToDevice));
+    VX_HIP(hipMemcpy(c->d_hy_roots.get(), roots_table, (size_t)n_pieces * 32, hipMemcpyHostToDevice));
     c->n_hy_table = n_pieces;
     return 0;
 }

@@ -415,9 +415,9 @@ struct SplitRun {
                 for (const Lane& l : lanes) {
                     const uint64_t L = plen(l.piece), clen = chunk_len(L, l.a, l.ramp);
                     if (one_round)
-                        runs.add(it, s.h_stage + (uint64_t)m * rp, l.piece, clen);
+                        runs.add(it, s.stage.get() + (uint64_t)m * rp, l.piece, clen);
                     else
-                        it.push_back(vx_files::ReadItem{s.h_stage + (uint64_t)m * rp, l.piece, l.a, clen});
+                        it.push_back(vx_files::ReadItem{s.stage.get() + (uint64_t)m * rp, l.piece, l.a, clen});
                     s.h_offsets[m] = (uint64_t)m * rp;
                     s.h_lens[m] = (uint32_t)clen;
                     s.h_pidx[m] = (uint32_t)(l.piece - first);
