@@ -78,6 +78,20 @@ int vx_tuning_zero_run_kernel(const uint32_t* d_pids, const uint32_t* d_poffs, c
  * Enqueue-only on `stream`. */
 int vx_tuning_zero_leaf_kernel(const uint32_t* d_rows, const uint32_t* d_lens, uint32_t n,
                                void* d_leaves, const void* full_row, void* stream);
+/* gather_kernel on its own (tests/test_gpu_gather_sweep.py):
+ * vx::launch_gather and nothing else.  Piece i is d_lens[i] bytes at the
+ * device-visible address d_src[i] and goes to d_arena + d_dst_off[i]; a piece
+ * the launch does not gather (d_src[i] == 0) or of no bytes owns no tile and
+ * is not touched.  The caller's contract, as the engine keeps it: d_arena,
+ * every gathered d_src[i] and every d_dst_off[i] are 16-byte aligned, piece i
+ * owns the 64 KiB tiles [d_tfirst[i], d_tfirst[i + 1]) (d_tfirst has n + 1
+ * entries, d_tfirst[i + 1] - d_tfirst[i] == ceil(d_lens[i] / 64 KiB) for a
+ * gathered piece and 0 otherwise), and ntiles == d_tfirst[n].  max_grid caps
+ * the workgroups of the launch, 0: the default of 64.  n == 0 or ntiles == 0
+ * launches nothing.  Enqueue-only on `stream`. */
+int vx_tuning_gather_kernel(const uint64_t* d_src, const uint64_t* d_dst_off, const uint32_t* d_lens,
+                            const uint32_t* d_tfirst, uint32_t n, uint32_t ntiles, void* d_arena, uint32_t max_grid,
+                            void* stream);
 /* The kernel that ends a hybrid download slot on its own (DESIGN.md §3.8,
  * §6.9; tests/test_gpu_hybrid_tail_sweep.py): lane j with d_pads[j] != 0
  * finishes its piece as the zero-tail kernel does (every padded piece is

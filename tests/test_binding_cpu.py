@@ -114,6 +114,8 @@ def test_parser_reads_every_prototype():
     assert len(protos["vx_merkle_hash_files_leaves"][1]) == 13 and protos["vx_last_error"] == ("charc *", [])
     assert protos["vx_tuning_zero_leaf_kernel"] == ("int", ["uint32_tc *", "uint32_tc *", "uint32_t", "void *",
                                                             "voidc *", "void *"])
+    assert protos["vx_tuning_gather_kernel"] == ("int", ["uint64_tc *", "uint64_tc *", "uint32_tc *", "uint32_tc *",
+                                                         "uint32_t", "uint32_t", "void *", "uint32_t", "void *"])
 
 
 def test_binding_matches_the_headers():
@@ -156,6 +158,12 @@ def _undeclared(table):
     del table["vx_tuning_zero_leaf_kernel"]
 
 
+def _gather_grid_as_pointer(table):
+    args = table["vx_tuning_gather_kernel"][0]
+    assert args[7] is ctypes.c_uint32  # the eighth argument goes to the stack: its width counts
+    args[7] = ctypes.c_void_p
+
+
 @pytest.mark.parametrize("doctor,needles", [
     (_narrow, ["vx_merkle_hash_files_leaves: argument 10 is uint32 in _lib.py, uint64 (`uint64_t`) in the header"]),
     (_drop, ["vx_tuning_hybrid_finish_kernel: 14 arguments in _lib.py, 15 in the header"]),
@@ -164,6 +172,8 @@ def _undeclared(table):
     (_int_return, ["vx_merkle_verify_files_blocks: returns int32 in _lib.py, int64 (`int64_t`) in the header"]),
     (_signed, ["vx_merkle_tree_proof: argument 5 is int64 in _lib.py, uint64 (`uint64_t`) in the header"]),
     (_undeclared, ["vx_tuning_zero_leaf_kernel: declared in the headers, not in _lib._declare"]),
+    (_gather_grid_as_pointer, ["vx_tuning_gather_kernel: argument 8 is pointer in _lib.py, uint32 (`uint32_t`) in "
+                               "the header"]),
 ])
 def test_checker_rejects_known_mistakes(doctor, needles):
     """The comparison bites: each doctored table is reported by function name

@@ -100,10 +100,12 @@ def test_tail_kernel_edges(built, gpu, pl):
     assert (got1, got2, m) == (want1, want2, None)
 
 
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 130])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 130, 255, 256, 257, 600])
 def test_mixed_waves(built, gpu, n):
     """The edge shapes of both piece lengths' data lengths at 64 KiB, shuffled,
-    so a wave's lanes mix Z from 0 to the maximum and pad-free lanes."""
+    so a wave's lanes mix Z from 0 to the maximum and pad-free lanes.  From 257
+    pieces on hybrid_prep_kernel and hybrid_merge_kernel (256 lanes a
+    workgroup) run a second workgroup, at 600 a third, partial one."""
     pl = 65536
     base = edge_shapes(pl)
     order = np.random.default_rng(n).permutation(len(base)).tolist()
@@ -113,6 +115,13 @@ def test_mixed_waves(built, gpu, n):
     assert [i for i in range(n) if got1[i] != want1[i]] == []
     assert [i for i in range(n) if got2[i] != want2[i]] == []
     assert m == [3] * n
+    # ... and with every third SHA-1 row and every fifth root wrong, so that each lane's verdict is its
+    # own: a verdict the merge kernel did not write (its output is not cleared first) cannot pass for one
+    e1 = [hashlib.sha1(w).digest() if i % 3 == 0 else w for i, w in enumerate(want1)]
+    e2 = [hashlib.sha256(w).digest() if i % 5 == 0 else w for i, w in enumerate(want2)]
+    got1, got2, m = run_device(gpu, pl, shapes, pieces, lw, e1, e2)
+    assert (got1, got2) == (want1, want2)
+    assert m == [(0 if i % 3 == 0 else 1) | (0 if i % 5 == 0 else 2) for i in range(n)]
 
 
 def test_one_byte_of_a_1mib_piece(built, gpu):

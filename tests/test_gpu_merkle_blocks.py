@@ -216,6 +216,30 @@ def test_damage_patterns(built, gpu, lw, n):
     assert words3 == b.words([range(k) for k in nblocks])
 
 
+def test_every_word_of_a_leaf_row_decides(built, gpu):
+    """64 blocks of one piece, 32 to 95 of its 128, so both of its bitmap words:
+    the stored leaf row of block k is one bit off, in word k % 8 (the bit moves
+    through the word with k).  The bitmap names exactly those blocks; a compare
+    that skipped one of the eight words would miss eight of them."""
+    lw, n = 7, 19
+    b = batch(lw, n)
+    victim = b.lens.index(BLOCK << lw)
+    blocks = list(range(32, 96))
+    exp = _garbage_past_end(b, random.Random(0x0B17))
+    for k in blocks:
+        row = bytearray(exp[victim * b.W + k])
+        assert bytes(row) == b.leaves[victim][k]
+        bit = (5 * k + 3) % 32
+        row[4 * (k % 8) + bit // 8] ^= 1 << (bit % 8)
+        exp[victim * b.W + k] = bytes(row)
+    assert {k % 8 for k in blocks} == set(range(8)) and len({(5 * k + 3) % 32 for k in blocks}) == 32
+    want = [blocks if i == victim else [] for i in range(n)]
+    words, raw = _run(b, gpu, None, exp)
+    assert words == b.words(want)
+    assert words[victim * b.wpp:(victim + 1) * b.wpp] == [0xFFFFFFFF00000000, 0x00000000FFFFFFFF]
+    assert raw == b"".join(b"".join(lv) for lv in b.leaves)  # the leaves written are the data's, not the stored rows
+
+
 def test_leaves_only_form(built, gpu):
     import torch
 

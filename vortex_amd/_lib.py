@@ -77,6 +77,7 @@ TUNING_EXPORTS = (
     "vx_tuning_wall_clock_khz", "vx_tuning_device_identity", "vx_tuning_split_take_tail",
     "vx_tuning_last_split", "vx_tuning_zero_tail_kernel", "vx_tuning_chunk_kernel",
     "vx_tuning_hybrid_finish_kernel", "vx_tuning_zero_run_kernel", "vx_tuning_zero_leaf_kernel",
+    "vx_tuning_gather_kernel",
 )
 
 
@@ -351,6 +352,7 @@ def _declare(L: ctypes.CDLL, tuning: bool = False) -> None:
                                                 vp, vp], c.c_int),
             "vx_tuning_zero_run_kernel": ([vp, vp, vp, c.c_uint32, vp, vp], c.c_int),
             "vx_tuning_zero_leaf_kernel": ([vp, vp, c.c_uint32, vp, vp, vp], c.c_int),
+            "vx_tuning_gather_kernel": ([vp, vp, vp, vp, c.c_uint32, c.c_uint32, vp, c.c_uint32, vp], c.c_int),
             "vx_tuning_fail_submit_after": ([vp, c.c_int64], None),
             "vx_tuning_fail_launch_after": ([vp, c.c_int64], None),
             "vx_tuning_verify_copy_stream": ([vp, c.c_int], None),

@@ -811,6 +811,21 @@ int vx_tuning_zero_copy_kernel(const uint64_t* d_srcs, const uint32_t* d_lens, u
     return e == hipSuccess ? 0 : hip_fail(e, "vx_tuning_zero_copy_kernel");
 }
 #ifdef VX_TEST_HOOKS
+int vx_tuning_gather_kernel(const uint64_t* d_src, const uint64_t* d_dst_off, const uint32_t* d_lens,
+                            const uint32_t* d_tfirst, uint32_t n, uint32_t ntiles, void* d_arena, uint32_t max_grid,
+                            void* stream) {
+    if (n == 0) return 0;
+    if (!d_src || !d_dst_off || !d_lens || !d_tfirst || !d_arena)
+        return fail(VX_EINVAL, "vx_tuning_gather_kernel: NULL argument");
+    if (((reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst_off)) & 7) ||
+        ((reinterpret_cast<uintptr_t>(d_lens) | reinterpret_cast<uintptr_t>(d_tfirst)) & 3) ||
+        (reinterpret_cast<uintptr_t>(d_arena) & 15))
+        return fail(VX_EINVAL, "vx_tuning_gather_kernel: d_src and d_dst_off must be 8-byte, d_lens and d_tfirst "
+                               "4-byte and d_arena 16-byte aligned");
+    hipError_t e = vx::launch_gather(d_src, d_dst_off, d_lens, d_tfirst, n, ntiles, static_cast<uint8_t*>(d_arena),
+                                     static_cast<hipStream_t>(stream), max_grid);
+    return e == hipSuccess ? 0 : hip_fail(e, "vx_tuning_gather_kernel");
+}
 void vx_tuning_fail_submit_after(vx_ctx* c, int64_t k) {
     if (c) c->fail_submit_after = k < 0 ? -1 : k;
 }

@@ -66,7 +66,8 @@ __global__ __launch_bounds__(kGatherBlock) void gather_kernel(const uint64_t* __
     }
 }
 
-uint32_t gather_tiles(uint32_t len) { return (len + kGatherTile - 1) / kGatherTile; }
+// (the sum in 64 bits: in 32 it wraps for lengths within a tile of 2^32)
+uint32_t gather_tiles(uint32_t len) { return (uint32_t)(((uint64_t)len + kGatherTile - 1) / kGatherTile); }
 
 // Grid size.  64 workgroups already move 52.8 GiB/s alone (256: 52.8, 32:
 // 52.3; profiles/r01/h2d/gather3.json), and a gather runs BESIDE hash kernels
