@@ -1,7 +1,9 @@
 """GPU: the SHA-256 merkle kernels at the edges the other merkle tests leave out.
 
-  * leaf lengths 128 g + r around the leaf kernels' two-group ring: the tail
-    lengths of test_gpu_merkle*.py all sit at g <= 1 or g = 127;
+  * leaf lengths 128 g + r around the leaf kernels' two-group ring, twelve
+    tails at seven group counts, each group count a wave of its own; every
+    tail 0..127, waves that mix group counts and each of the five entries of
+    the leaf lane on its own are in test_gpu_merkle_leaf_sweep.py;
   * per-piece widths (log2w) under a batch wider than one node tile
     (log2_width = 10, the smallest such width; widths 11 to 17, where the
     wide kernels have more than two tiles per piece, are in
