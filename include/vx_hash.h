@@ -643,14 +643,34 @@ typedef struct vx_merkle_completion {
  * and v2 pieces share the context's batch slots, pending count, vx_flush,
  * vx_drain and statistics; a slot holds one kind, so a change of kind launches
  * the open batch.  A v2 slot is always copied or gathered into HBM first
- * (never hashed zero-copy) and hashed by the fused piece kernel: one launch
- * for trees of at most 256 leaves, two above. */
+ * (not hashed zero-copy unless vx_set_merkle_zero_copy) and hashed by the
+ * fused piece kernel: one launch for trees of at most 256 leaves, two above. */
 int vx_merkle_submit(vx_ctx* ctx, uint64_t tag, const uint8_t* data, uint32_t len, uint32_t log2w,
                      const uint8_t* expected);
 /* vx_poll for v2 pieces: vx_poll hands out v1 completions only, this call v2
  * only.  After a device failure each returns the results it still holds, then
  * the error. */
 int64_t vx_merkle_poll(vx_ctx* ctx, vx_merkle_completion* out, size_t max);
+/* Zero-copy for the v2 download path, off by default.  on = 1: a v2 slot whose
+ * every piece lies in registered host memory at a 16-byte aligned address (what
+ * makes a v1 slot zero-copy) is hashed by the zero-copy piece kernel straight
+ * through the pieces' device mappings: no gather, no copy, no wait on the copy
+ * chain, so the slot's PCIe transfer overlaps its own hashing.  Any other v2
+ * slot takes the gathered path as with on = 0.  Roots, verdicts, completions
+ * and vx_get_stats are the same either way (zero_copy_slots stays v1's, and
+ * gather_tiles counts a zero-copy v2 slot's tiles as the gathered path would);
+ * what the setting did is in the trace.  Read when a slot is launched, so it may
+ * change while pieces are pending.  Hybrid slots, vx_merkle_verify_batch,
+ * vx_merkle_check_blocks and the files calls do not look at it.
+ * VX_EINVAL: NULL ctx, or on not 0/1. */
+int vx_set_merkle_zero_copy(vx_ctx* ctx, int on);
+/* Since vx_create: v2 slots launched zero-copy, their pieces and bytes, and v2
+ * slots launched the gathered way while the setting was on.  (An unnamed
+ * struct: the type is its typedef.) */
+typedef struct {
+    uint64_t slots, pieces, bytes, fallback_slots;
+} vx_merkle_zc_trace;
+int vx_merkle_zero_copy_trace(const vx_ctx* ctx, vx_merkle_zc_trace* out);
 
 /* The two halves of the device entries on their own, for a caller that
  * streams blocks in rounds of its own (the re-verify below does).

@@ -78,6 +78,24 @@ int vx_tuning_zero_run_kernel(const uint32_t* d_pids, const uint32_t* d_poffs, c
  * Enqueue-only on `stream`. */
 int vx_tuning_zero_leaf_kernel(const uint32_t* d_rows, const uint32_t* d_lens, uint32_t n,
                                void* d_leaves, const void* full_row, void* stream);
+/* merkle_zc_piece_kernel on its own (vx_set_merkle_zero_copy, DESIGN.md §3.7;
+ * tests/test_gpu_merkle_zc_sweep.py): the launch and, above 256 leaves, the
+ * node pass over the tile tops, and nothing else.  Piece i is d_lens[i] bytes
+ * at the device-visible address d_srcs[i] (HBM, or a registered host buffer's
+ * device mapping; 16-byte aligned; not read when d_lens[i] == 0), its tree has
+ * 2^d_log2w[i] leaf slots (NULL: 2^log2_width), d_lens[i] <= 16384 <<
+ * d_log2w[i] and d_log2w[i] <= log2_width; d_roots n x 32 B and / or d_expected
+ * with d_matched, as vx_merkle_device_pieces takes them.  The tile tops are the
+ * call's own (one process-wide block, grown on demand: calls on different
+ * streams must not overlap above log2_width 8).  Enqueue-only on `stream`. */
+int vx_tuning_merkle_zc_kernel(const uint64_t* d_srcs, const uint32_t* d_lens, const uint8_t* d_log2w, uint32_t n,
+                               uint32_t log2_width, void* d_roots, const void* d_expected, void* d_matched,
+                               void* stream);
+/* That kernel's geometry (host-only): out[0] leaf rows per workgroup, out[1]
+ * leaves a wave loads and hashes, out[2] bytes per leaf per cooperative tile,
+ * out[3] tiles in flight per wave.  LDS per workgroup: out[0] / out[1] stages
+ * of out[2] / 16 rows of out[1] + 1 16-byte slots, and out[0] 32-byte rows. */
+void vx_tuning_merkle_zc_geometry(uint32_t* out); /* out[4] */
 /* gather_kernel on its own (tests/test_gpu_gather_sweep.py):
  * vx::launch_gather and nothing else.  Piece i is d_lens[i] bytes at the
  * device-visible address d_src[i] and goes to d_arena + d_dst_off[i]; a piece

@@ -14,8 +14,13 @@
 // calls first; every 97th is planted wrong).  Prints one JSON line with each
 // leg's figure and the medians.
 //
-// usage: merkle_async_probe burst <piece_len> [total_bytes=2147483648] [reps=5]
-//        merkle_async_probe loop  <piece_len> [batch=32] [batches=200] [reps=5]
+// A last argument `zc` adds a third kind of leg: v2 with vx_set_merkle_zero_copy
+// on (the slots hashed straight out of the registered buffers), alternating
+// with the v1 legs and the gathered v2 legs in the same process; its figures
+// are the "v2zc_" keys and the trace of vx_merkle_zero_copy_trace.
+//
+// usage: merkle_async_probe burst <piece_len> [total_bytes=2147483648] [reps=5] [zc]
+//        merkle_async_probe loop  <piece_len> [batch=32] [batches=200] [reps=5] [zc]
 #include <sys/mman.h>
 
 #include <algorithm>
@@ -86,6 +91,9 @@ int main(int argc, char** argv) {
         return 2;
     }
     const bool burst = !std::strcmp(argv[1], "burst");
+    const bool zc = !std::strcmp(argv[argc - 1], "zc");
+    if (zc) --argc;
+    const int kinds = zc ? 3 : 2;  // 0: v1, 1: v2 gathered, 2: v2 zero-copy
     Probe p;
     p.plen = (uint32_t)std::strtoul(argv[2], nullptr, 0);
     const uint64_t total = burst && argc > 3 ? std::strtoull(argv[3], nullptr, 0) : 2ull << 30;
@@ -155,18 +163,23 @@ int main(int argc, char** argv) {
         return 0;
     };
     const uint32_t rounds = burst ? 1 : batches;
-    std::vector<double> fig[2], p99[2];  // per leg: GiB/s (burst) or p50 seconds (loop)
+    std::vector<double> fig[3], p99[3];  // per kind: GiB/s (burst) or p50 seconds (loop)
     double s = 0;
-    for (int v2 = 0; v2 < 2 && !rc; ++v2) rc = leg(v2 != 0, burst ? 1 : 8, nullptr, &s);  // warm both kinds' buffers
+    auto kind_leg = [&](int kind, uint32_t n_rounds, std::vector<double>* lat) -> int {
+        if (zc)
+            if (int e = vx_set_merkle_zero_copy(p.ctx, kind == 2)) return e;
+        return leg(kind != 0, n_rounds, lat, &s);
+    };
+    for (int k = 0; k < kinds && !rc; ++k) rc = kind_leg(k, burst ? 1 : 8, nullptr);  // warm every kind's buffers
     for (int r = 0; r < reps && !rc; ++r) {
-        for (int v2 = 0; v2 < 2 && !rc; ++v2) {
+        for (int k = 0; k < kinds && !rc; ++k) {
             std::vector<double> lat;
-            rc = leg(v2 != 0, rounds, &lat, &s);
+            rc = kind_leg(k, rounds, &lat);
             if (burst) {
-                fig[v2].push_back((double)p.nbuf * p.plen / s / (double)(1ull << 30));
+                fig[k].push_back((double)p.nbuf * p.plen / s / (double)(1ull << 30));
             } else {
-                fig[v2].push_back(pct(lat, 0.5));
-                p99[v2].push_back(pct(lat, 0.99));
+                fig[k].push_back(pct(lat, 0.5));
+                p99[k].push_back(pct(lat, 0.99));
             }
         }
     }
@@ -176,6 +189,23 @@ int main(int argc, char** argv) {
     }
     vx_stats st{};
     vx_get_stats(p.ctx, &st);
+    vx_merkle_zc_trace tr{};
+    vx_merkle_zero_copy_trace(p.ctx, &tr);
+    char zcs[512] = "";
+    if (zc && burst)
+        std::snprintf(zcs, sizeof zcs, ", \"v2zc_GiBps\": %s, \"v2zc_GiBps_median\": %.3f, \"v2zc_over_v2\": %.3f, "
+                      "\"zc_trace\": {\"slots\": %llu, \"pieces\": %llu, \"bytes\": %llu, \"fallback_slots\": %llu}",
+                      list(fig[2], 1).c_str(), pct(fig[2], 0.5), pct(fig[2], 0.5) / pct(fig[1], 0.5),
+                      (unsigned long long)tr.slots, (unsigned long long)tr.pieces, (unsigned long long)tr.bytes,
+                      (unsigned long long)tr.fallback_slots);
+    else if (zc)
+        std::snprintf(zcs, sizeof zcs, ", \"v2zc_p50_ms\": %s, \"v2zc_p99_ms\": %s, \"v2zc_p50_ms_median\": %.3f, "
+                      "\"v2zc_p99_ms_median\": %.3f, \"v2zc_over_v2_p50\": %.3f, "
+                      "\"zc_trace\": {\"slots\": %llu, \"pieces\": %llu, \"bytes\": %llu, \"fallback_slots\": %llu}",
+                      list(fig[2], 1e3).c_str(), list(p99[2], 1e3).c_str(), pct(fig[2], 0.5) * 1e3,
+                      pct(p99[2], 0.5) * 1e3, pct(fig[2], 0.5) / pct(fig[1], 0.5), (unsigned long long)tr.slots,
+                      (unsigned long long)tr.pieces, (unsigned long long)tr.bytes,
+                      (unsigned long long)tr.fallback_slots);
     for (uint32_t b = 0; b < p.nbuf; ++b) {
         vx_unregister_host_buffer(p.ctx, p.bufs[b]);
         munmap(p.bufs[b], p.plen);
@@ -184,20 +214,20 @@ int main(int argc, char** argv) {
     if (burst) {
         std::printf("{\"mode\": \"burst\", \"piece_len\": %u, \"pieces\": %u, \"bytes\": %llu, \"reps\": %d, "
                     "\"v1_GiBps\": %s, \"v2_GiBps\": %s, \"v1_GiBps_median\": %.3f, \"v2_GiBps_median\": %.3f, "
-                    "\"v2_over_v1\": %.3f, \"zero_copy_slots\": %llu, \"gather_tiles\": %llu, \"wrong_verdicts\": %llu}\n",
+                    "\"v2_over_v1\": %.3f, \"zero_copy_slots\": %llu, \"gather_tiles\": %llu, \"wrong_verdicts\": %llu%s}\n",
                     p.plen, p.nbuf, (unsigned long long)p.nbuf * p.plen, reps, list(fig[0], 1).c_str(),
                     list(fig[1], 1).c_str(), pct(fig[0], 0.5), pct(fig[1], 0.5), pct(fig[1], 0.5) / pct(fig[0], 0.5),
                     (unsigned long long)st.zero_copy_slots, (unsigned long long)st.gather_tiles,
-                    (unsigned long long)p.wrong);
+                    (unsigned long long)p.wrong, zcs);
     } else {
         std::printf("{\"mode\": \"loop\", \"piece_len\": %u, \"batch\": %u, \"batches_per_leg\": %u, \"reps\": %d, "
                     "\"v1_p50_ms\": %s, \"v2_p50_ms\": %s, \"v1_p99_ms\": %s, \"v2_p99_ms\": %s, "
                     "\"v1_p50_ms_median\": %.3f, \"v2_p50_ms_median\": %.3f, \"v1_p99_ms_median\": %.3f, "
-                    "\"v2_p99_ms_median\": %.3f, \"v2_over_v1_p50\": %.3f, \"wrong_verdicts\": %llu}\n",
+                    "\"v2_p99_ms_median\": %.3f, \"v2_over_v1_p50\": %.3f, \"wrong_verdicts\": %llu%s}\n",
                     p.plen, batch, batches, reps, list(fig[0], 1e3).c_str(), list(fig[1], 1e3).c_str(),
                     list(p99[0], 1e3).c_str(), list(p99[1], 1e3).c_str(), pct(fig[0], 0.5) * 1e3,
                     pct(fig[1], 0.5) * 1e3, pct(p99[0], 0.5) * 1e3, pct(p99[1], 0.5) * 1e3,
-                    pct(fig[1], 0.5) / pct(fig[0], 0.5), (unsigned long long)p.wrong);
+                    pct(fig[1], 0.5) / pct(fig[0], 0.5), (unsigned long long)p.wrong, zcs);
     }
     return p.wrong == 0 ? 0 : 3;
 }

@@ -66,6 +66,7 @@ EXPORTS = (
     "vx_set_skip_holes", "vx_last_verify_holes", "vx_sha1_device_zeros", "vx_merkle_device_zero_leaves",
     "vx_merkle_leaf_rows", "vx_merkle_device_leaf_check", "vx_merkle_verify_files_blocks",
     "vx_merkle_verify_files_blocks_range", "vx_merkle_hash_files_leaves", "vx_merkle_hash_files_leaves_range",
+    "vx_set_merkle_zero_copy", "vx_merkle_zero_copy_trace",
 )
 # ... plus include/vx_tuning.h and include/vx_synth.h: libvortex_amd_tuning.so only.
 TUNING_EXPORTS = (
@@ -77,7 +78,7 @@ TUNING_EXPORTS = (
     "vx_tuning_wall_clock_khz", "vx_tuning_device_identity", "vx_tuning_split_take_tail",
     "vx_tuning_last_split", "vx_tuning_zero_tail_kernel", "vx_tuning_chunk_kernel",
     "vx_tuning_hybrid_finish_kernel", "vx_tuning_zero_run_kernel", "vx_tuning_zero_leaf_kernel",
-    "vx_tuning_gather_kernel",
+    "vx_tuning_gather_kernel", "vx_tuning_merkle_zc_kernel", "vx_tuning_merkle_zc_geometry",
 )
 
 
@@ -201,6 +202,21 @@ class vx_hole_trace(ctypes.Structure):
         ("scan_ms", ctypes.c_double), ("zero_hash_ms", ctypes.c_double)]
 
 
+MERKLE_ZC_TRACE_FIELDS = ("slots", "pieces", "bytes", "fallback_slots")
+_made = {}
+
+
+def merkle_zc_trace_type():
+    """The ctypes form of vx_merkle_zc_trace (vx_merkle_zero_copy_trace): four
+    uint64_t, 32 bytes.  In C the struct has no tag, only its typedef, so it is
+    not one of the module's tagged structures; made on first use, and its
+    layout is checked against the header by tests/test_merkle_zc_cpu.py."""
+    if "vx_merkle_zc_trace" not in _made:
+        _made["vx_merkle_zc_trace"] = type("vx_merkle_zc_trace", (ctypes.Structure,),
+                                           {"_fields_": [(name, ctypes.c_uint64) for name in MERKLE_ZC_TRACE_FIELDS]})
+    return _made["vx_merkle_zc_trace"]
+
+
 VX_ROUND_NEW_WINDOW, VX_ROUND_HEAD_RAMP, VX_ROUND_TAIL_RAMP = 1, 2, 4
 
 
@@ -262,6 +278,8 @@ def _declare(L: ctypes.CDLL, tuning: bool = False) -> None:
         "vx_last_verify_rounds": ([vp, c.POINTER(vx_verify_round), c.c_size_t], c.c_int64),
         "vx_set_skip_holes": ([vp, c.c_int], c.c_int),
         "vx_last_verify_holes": ([vp, c.POINTER(vx_hole_trace)], c.c_int),
+        "vx_set_merkle_zero_copy": ([vp, c.c_int], c.c_int),
+        "vx_merkle_zero_copy_trace": ([vp, c.POINTER(merkle_zc_trace_type())], c.c_int),
         "vx_sha1_device_zeros": ([vp, c.c_uint32, vp, vp], c.c_int),
         "vx_merkle_device_zero_leaves": ([vp, c.c_uint32, vp, vp], c.c_int),
         "vx_plan_verify": ([c.c_uint64, c.c_uint32, c.c_uint64, c.c_uint32, c.c_double, c.POINTER(vx_plan)], c.c_int),
@@ -353,6 +371,8 @@ def _declare(L: ctypes.CDLL, tuning: bool = False) -> None:
             "vx_tuning_zero_run_kernel": ([vp, vp, vp, c.c_uint32, vp, vp], c.c_int),
             "vx_tuning_zero_leaf_kernel": ([vp, vp, c.c_uint32, vp, vp, vp], c.c_int),
             "vx_tuning_gather_kernel": ([vp, vp, vp, vp, c.c_uint32, c.c_uint32, vp, c.c_uint32, vp], c.c_int),
+            "vx_tuning_merkle_zc_kernel": ([vp, vp, vp, c.c_uint32, c.c_uint32, vp, vp, vp, vp], c.c_int),
+            "vx_tuning_merkle_zc_geometry": ([c.POINTER(c.c_uint32)], None),
             "vx_tuning_fail_submit_after": ([vp, c.c_int64], None),
             "vx_tuning_fail_launch_after": ([vp, c.c_int64], None),
             "vx_tuning_verify_copy_stream": ([vp, c.c_int], None),

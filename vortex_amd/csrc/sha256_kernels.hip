@@ -30,6 +30,11 @@
 //    workgroup's 256 leaf rows stay in LDS and are reduced there; trees of at
 //    most 256 leaves finish in the one launch, wider ones leave a top per
 //    256-leaf tile for the node kernel.  No leaf layer is kept.
+//  * zero-copy piece kernel (vx_set_merkle_zero_copy): the piece kernel with
+//    each piece at a device-visible address of its own (a registered host
+//    buffer's mapping) and a cooperative leaf phase: a wave loads 256 bytes of
+//    each of its 64 leaves per tile, two tiles in flight, and transposes them
+//    through LDS to the lane that owns the leaf.  The tree phase is shared.
 //  * block check kernel (vx_merkle_device_block_check): the leaf kernel's
 //    lanes, each comparing its leaf with an expected row; a wave's verdicts
 //    leave as one ballot, a bit per 16 KiB block.
@@ -410,6 +415,43 @@ struct PieceRows {
     uint4 hi[kBlock];
 };
 
+// The tree phase of the piece kernels: the workgroup's 256 leaf rows are in t
+// (a barrier behind the last write); every thread of the workgroup calls this.
+__device__ __forceinline__ void piece_tree_phase(PieceRows& t, const uint8_t* __restrict__ log2w, uint32_t n,
+                                                 uint32_t log2_width, uint8_t* __restrict__ tops,
+                                                 uint8_t* __restrict__ log2w_top, uint8_t* __restrict__ roots,
+                                                 const uint8_t* __restrict__ expected, uint8_t* __restrict__ matched) {
+    const uint32_t i = threadIdx.x;
+    if (log2_width <= (uint32_t)kPieceTileLog2) {
+        const uint32_t per = (uint32_t)kBlock >> log2_width;  // pieces of this workgroup: one thread each
+        const uint32_t piece = blockIdx.x * per + i;
+        const bool mine = i < per && piece < n;
+        const uint32_t want = mine ? (log2w ? log2w[piece] : log2_width) : 0xFFFFFFFFu;
+        for (uint32_t L = 0;; ++L) {
+            if (want == L)
+                emit_root(Row{t.lo[(i << log2_width) >> L], t.hi[(i << log2_width) >> L]}, piece, roots, expected,
+                          matched);
+            if (L == log2_width) break;
+            reduce_level(t, (uint32_t)kBlock >> (L + 1));
+        }
+    } else {
+        const uint32_t tshift = log2_width - kPieceTileLog2;
+        const uint32_t piece = blockIdx.x >> tshift;  // (< n: n << log2_width rows are whole tiles)
+        const uint32_t tile = blockIdx.x & ((1u << tshift) - 1);
+        const uint32_t want = log2w ? log2w[piece] : log2_width;  // (workgroup-uniform)
+        const uint32_t levels = want < (uint32_t)kPieceTileLog2 ? want : (uint32_t)kPieceTileLog2;
+        // (a log2w above log2_width is not a level of this tree: clamped, it stays in bounds and emits nothing)
+        const uint32_t want_top = want - levels < tshift + 1 ? want - levels : tshift + 1;
+        for (uint32_t L = 0; L < levels; ++L) reduce_level(t, (uint32_t)kBlock >> (L + 1));
+        if (i == 0 && tile < (1u << want_top)) {
+            uint4* o = reinterpret_cast<uint4*>(tops + ((size_t)(piece << tshift) + tile) * 32);
+            o[0] = t.lo[0];
+            o[1] = t.hi[0];
+            if (tile == 0) log2w_top[piece] = (uint8_t)want_top;
+        }
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void merkle_piece_kernel(const uint8_t* __restrict__ base,
                                                               const uint64_t* __restrict__ offsets,
                                                               const uint32_t* __restrict__ lens,
@@ -451,34 +493,154 @@ __global__ __launch_bounds__(kBlock) void merkle_piece_kernel(const uint8_t* __r
         t.hi[i] = make_uint4(sha256::bswap(s.h[4]), sha256::bswap(s.h[5]), sha256::bswap(s.h[6]), sha256::bswap(s.h[7]));
     }
     __syncthreads();
-    if (log2_width <= (uint32_t)kPieceTileLog2) {
-        const uint32_t per = (uint32_t)kBlock >> log2_width;  // pieces of this workgroup: one thread each
-        const uint32_t piece = blockIdx.x * per + i;
-        const bool mine = i < per && piece < n;
-        const uint32_t want = mine ? (log2w ? log2w[piece] : log2_width) : 0xFFFFFFFFu;
-        for (uint32_t L = 0;; ++L) {
-            if (want == L)
-                emit_root(Row{t.lo[(i << log2_width) >> L], t.hi[(i << log2_width) >> L]}, piece, roots, expected,
-                          matched);
-            if (L == log2_width) break;
-            reduce_level(t, (uint32_t)kBlock >> (L + 1));
-        }
-    } else {
-        const uint32_t tshift = log2_width - kPieceTileLog2;
-        const uint32_t piece = blockIdx.x >> tshift;  // (< n: n << log2_width rows are whole tiles)
-        const uint32_t tile = blockIdx.x & ((1u << tshift) - 1);
-        const uint32_t want = log2w ? log2w[piece] : log2_width;  // (workgroup-uniform)
-        const uint32_t levels = want < (uint32_t)kPieceTileLog2 ? want : (uint32_t)kPieceTileLog2;
-        // (a log2w above log2_width is not a level of this tree: clamped, it stays in bounds and emits nothing)
-        const uint32_t want_top = want - levels < tshift + 1 ? want - levels : tshift + 1;
-        for (uint32_t L = 0; L < levels; ++L) reduce_level(t, (uint32_t)kBlock >> (L + 1));
-        if (i == 0 && tile < (1u << want_top)) {
-            uint4* o = reinterpret_cast<uint4*>(tops + ((size_t)(piece << tshift) + tile) * 32);
-            o[0] = t.lo[0];
-            o[1] = t.hi[0];
-            if (tile == 0) log2w_top[piece] = (uint8_t)want_top;
-        }
+    piece_tree_phase(t, log2w, n, log2_width, tops, log2w_top, roots, expected, matched);
+}
+
+// ---------------------------------------------------------------------------
+// Zero-copy piece kernel (vx_set_merkle_zero_copy):
+// merkle_piece_kernel with piece i at the device-visible address srcs[i] (HBM,
+// or a registered host buffer's mapping; 16-byte aligned) instead of base +
+// offsets[i], so a v2 slot's PCIe transfer overlaps its own hashing.  Thread i
+// of a workgroup still owns leaf row i of the workgroup's 256 and the tree
+// phase is piece_tree_phase; only the leaf phase differs.  Over PCIe the load
+// shape decides the rate (sha1_zc_split_kernel's comment): one lane streaming
+// its own leaf reaches 28-31 GiB/s, so the loads are cooperative.
+//  * A wave serves its own 64 leaves.  A tile is kZcTileBytes = 256 contiguous
+//    bytes of each of them: 16 wave instructions, each 16 lanes x 16 bytes on
+//    each of 4 leaves (the shape §6.5 measured), 16 KiB per wave and tile.
+//  * kZcInFlight = 2 tiles are in flight per wave in two register tiles (ra,
+//    rb): while tile t is hashed, t + 1 and t + 2 are on the wire, 32 KiB per
+//    wave, 128 KiB per workgroup, so a slot of 8 workgroups or more (2,048
+//    leaves: 32 pieces of 1 MiB) has the ~1 MiB in flight that the SHA-1
+//    kernel needed to reach the copy rate.
+//  * A landed tile is transposed through the wave's own LDS stage (chunk c of
+//    leaf l at [c][l], rows padded to 65 slots: lane-linear reads, and writes
+//    that spread a 16-lane group over all banks) to the lane that owns the
+//    leaf, which compresses its four 64-byte blocks.  There is no chain
+//    between leaves, so a wave stages and hashes for itself: LDS executes a
+//    wave's accesses in order, and wavefront-scope fences keep the compiler
+//    from moving them; no workgroup barrier before the tree phase.
+//  * The loop bound is the wave's largest tile count.  A load whose leaf has no
+//    full tile left (t >= leaf_len >> 8; every lane of a tile of the prefetch
+//    past the end) reads the device zero line, so no cooperative load touches a
+//    byte at or past the end of a leaf's last full tile.  The < 256 bytes
+//    behind it are the owning lane's (finish_tail: byte-exact, the padding from
+//    those bytes only); a leaf slot at or past the piece's end (a piece of 0
+//    bytes: every slot) and a lane past the launch's rows read nothing and give
+//    the zero row.
+constexpr uint32_t kZcLeavesPerWave = 64;
+constexpr uint32_t kZcTileBytes = 256;                  // bytes per leaf per tile
+constexpr uint32_t kZcTileChunks = kZcTileBytes / 16;   // 16-byte chunks per leaf per tile = wave instructions per tile
+constexpr uint32_t kZcInFlight = 2;                     // register tiles per wave
+constexpr uint32_t kZcStageRow = kZcLeavesPerWave + 1;  // padded
+static_assert(kZcLeavesPerWave == 64 && kZcTileChunks == 16, "an instruction is 16 lanes on each of 4 leaves");
+
+typedef uint32_t U32x4 __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(1))) U32x4 GlobalU32x4;
+
+struct ZcStage {
+    uint4 c[kBlock / 64][kZcTileChunks][kZcStageRow];
+};
+constexpr uint32_t kZcLdsBytes = sizeof(ZcStage) + sizeof(PieceRows);
+static_assert(2 * kZcLdsBytes <= 160 * 1024, "two workgroups per CU");
+
+// This lane's 16 loads of tile t: instruction k moves chunk lane & 15 of leaf
+// 4k + (lane >> 4).  zb[k]: that chunk's address in tile 0, zn[k]: the leaf's
+// full tiles.  Explicitly global vector loads, as zc_load of the SHA-1 kernel.
+__device__ __forceinline__ void zc_leaf_tile(uint4 (&r)[kZcTileChunks], const uint64_t (&zb)[kZcTileChunks],
+                                             const uint32_t (&zn)[kZcTileChunks], uint32_t t) {
+    const uint64_t zero = reinterpret_cast<uint64_t>(g_zero_group);
+#pragma unroll
+    for (uint32_t k = 0; k < kZcTileChunks; ++k) {
+        const uint64_t a = t < zn[k] ? zb[k] + (uint64_t)t * kZcTileBytes : zero;
+        const U32x4 v = *reinterpret_cast<GlobalU32x4*>(a);
+        r[k] = make_uint4(v.x, v.y, v.z, v.w);
     }
+}
+
+// Tile t (landed in r) through the wave's stage into the owning lanes' states,
+// r refilled with tile t_next behind the stage writes.
+__device__ __forceinline__ void zc_leaf_step(State& s, uint4 (&r)[kZcTileChunks], uint4 (&st)[kZcTileChunks][kZcStageRow],
+                                             const uint64_t (&zb)[kZcTileChunks], const uint32_t (&zn)[kZcTileChunks],
+                                             uint32_t t, uint32_t t_next, uint32_t nt, uint32_t lane) {
+#pragma unroll
+    for (uint32_t k = 0; k < kZcTileChunks; ++k) st[lane & 15][4 * k + (lane >> 4)] = r[k];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    zc_leaf_tile(r, zb, zn, t_next);
+    if (t < nt) {
+#pragma unroll
+        for (uint32_t b = 0; b < kZcTileChunks / 4; ++b)
+            sha256::compress_le(s, st[4 * b][lane], st[4 * b + 1][lane], st[4 * b + 2][lane], st[4 * b + 3][lane]);
+    }
+    // the stage is read before the next tile's writes
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ __launch_bounds__(kBlock) void merkle_zc_piece_kernel(const uint64_t* __restrict__ srcs,
+                                                                 const uint32_t* __restrict__ lens,
+                                                                 const uint8_t* __restrict__ log2w, uint32_t n,
+                                                                 uint32_t log2_width, uint8_t* __restrict__ tops,
+                                                                 uint8_t* __restrict__ log2w_top,
+                                                                 uint8_t* __restrict__ roots,
+                                                                 const uint8_t* __restrict__ expected,
+                                                                 uint8_t* __restrict__ matched) {
+    __shared__ PieceRows t;
+    __shared__ ZcStage stage;
+    const uint32_t i = threadIdx.x;
+    {
+        const uint32_t lane = i & 63u;
+        const uint32_t wave = __builtin_amdgcn_readfirstlane(i >> 6);
+        const uint32_t g = blockIdx.x * kBlock + i;
+        const uint32_t rows = n << log2_width;
+        // Lanes past the last row read their tables at row rows-1 (in bounds) and hash nothing;
+        // their LDS rows belong to pieces >= n and are never emitted.
+        const uint32_t gg = g < rows ? g : rows - 1;
+        const uint32_t piece = gg >> log2_width;
+        const uint32_t slot = gg & ((1u << log2_width) - 1);
+        const uint32_t plen = lens[piece];
+        const uint64_t start = (uint64_t)slot * kLeaf;
+        const uint32_t leaf_len =
+            g < rows && start < plen ? (plen - start < kLeaf ? (uint32_t)(plen - start) : kLeaf) : 0;
+        const uint64_t p = srcs[piece] + (leaf_len ? start : 0);  // (not an address of anything when leaf_len == 0)
+        const uint32_t nt = leaf_len / kZcTileBytes;
+        const uint32_t nt_wave = __builtin_amdgcn_readfirstlane(wave_max(nt));
+        State s = sha256::iv();
+        if (nt_wave) {  // (wave-uniform)
+            uint64_t zb[kZcTileChunks];
+            uint32_t zn[kZcTileChunks];
+#pragma unroll
+            for (uint32_t k = 0; k < kZcTileChunks; ++k) {
+                const int l = (int)(4 * k + (lane >> 4));
+                const uint32_t lo = __shfl((uint32_t)p, l, 64), hi = __shfl((uint32_t)(p >> 32), l, 64);
+                zb[k] = (((uint64_t)hi << 32) | lo) + 16u * (lane & 15u);
+                zn[k] = __shfl(nt, l, 64);
+            }
+            uint4 ra[kZcTileChunks], rb[kZcTileChunks];
+            zc_leaf_tile(ra, zb, zn, 0);
+            zc_leaf_tile(rb, zb, zn, 1);
+            for (uint32_t t0 = 0; t0 < nt_wave; t0 += kZcInFlight) {
+                zc_leaf_step(s, ra, stage.c[wave], zb, zn, t0, t0 + 2, nt, lane);
+                zc_leaf_step(s, rb, stage.c[wave], zb, zn, t0 + 1, t0 + 3, nt, lane);
+            }
+        }
+        if (leaf_len == kLeaf) {
+            sha256::compress_const(s, kPadLeaf);
+        } else if (leaf_len) {
+            finish_tail(s, reinterpret_cast<const uint8_t*>(p + (uint64_t)nt * kZcTileBytes),
+                        leaf_len % kZcTileBytes, leaf_len);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s.h[k] = 0;  // beyond the piece: the zero hash, not a hash of anything
+        }
+        t.lo[i] = make_uint4(sha256::bswap(s.h[0]), sha256::bswap(s.h[1]), sha256::bswap(s.h[2]), sha256::bswap(s.h[3]));
+        t.hi[i] = make_uint4(sha256::bswap(s.h[4]), sha256::bswap(s.h[5]), sha256::bswap(s.h[6]), sha256::bswap(s.h[7]));
+    }
+    __syncthreads();
+    piece_tree_phase(t, log2w, n, log2_width, tops, log2w_top, roots, expected, matched);
 }
 
 // Trees of at most kTile leaves: workgroup b reduces rows [b*kTile, +kTile) =
@@ -855,6 +1017,29 @@ hipError_t launch_merkle_pieces(const uint8_t* base, const uint64_t* offsets, co
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !wide) return e;
     return launch_nodes(n, top_width, work, log2w_top, roots, expected, matched, stream);
+}
+
+hipError_t launch_merkle_zc_pieces(const uint64_t* srcs, const uint32_t* lens, const uint8_t* log2w, uint32_t n,
+                                   uint32_t log2_width, uint8_t* work, uint8_t* roots, const uint8_t* expected,
+                                   uint8_t* matched, hipStream_t stream) {
+    if (n == 0 || (!roots && !(expected && matched))) return hipSuccess;
+    const uint64_t rows = (uint64_t)n << log2_width;
+    const uint32_t grid = (uint32_t)((rows + kBlock - 1) / kBlock);
+    const bool wide = log2_width > (uint32_t)kPieceTileLog2;
+    const uint32_t top_width = wide ? log2_width - kPieceTileLog2 : 0;
+    uint8_t* log2w_top = wide ? work + ((size_t)n << top_width) * 32 : nullptr;
+    hipLaunchKernelGGL(merkle_zc_piece_kernel, dim3(grid), dim3(kBlock), 0, stream, srcs, lens, log2w, n, log2_width,
+                       wide ? work : nullptr, log2w_top, roots, expected, matched);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !wide) return e;
+    return launch_nodes(n, top_width, work, log2w_top, roots, expected, matched, stream);
+}
+
+void merkle_zc_geometry(uint32_t out[4]) {
+    out[0] = kBlock;
+    out[1] = kZcLeavesPerWave;
+    out[2] = kZcTileBytes;
+    out[3] = kZcInFlight;
 }
 
 hipError_t launch_merkle_block_check(const uint8_t* base, const uint64_t* offsets, const uint32_t* lens, uint32_t n,

@@ -207,6 +207,9 @@ struct vx_ctx {
     std::deque<vx_completion> done;
     std::deque<vx_merkle_completion> done_v2;  // v2 pieces' results (vx_merkle_poll)
     std::deque<vx_hybrid_completion> done_hy;  // hybrid pieces' results (vx_hybrid_poll)
+    // vx_set_merkle_zero_copy: read by launch_v2 at every launch; what it did since vx_create
+    int merkle_zc = 0;
+    vx_merkle_zc_trace merkle_zc_trace{};
     // Hybrid download path: the device-resident v1 `pieces`
     // table and v2 rows (vx_hybrid_set_piece_tables), and the one side stream
     // every hybrid slot's merkle work runs on, beside the slot's SHA-1 chain;

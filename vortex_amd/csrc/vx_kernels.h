@@ -157,6 +157,16 @@ inline uint64_t merkle_pieces_work(uint32_t n, uint32_t log2_width) {  // bytes 
 hipError_t launch_merkle_pieces(const uint8_t* base, const uint64_t* offsets, const uint32_t* lens,
                                 const uint8_t* log2w, uint32_t n, uint32_t log2_width, uint8_t* work, uint8_t* roots,
                                 const uint8_t* expected, uint8_t* matched, hipStream_t stream);
+// The zero-copy piece kernel (vx_set_merkle_zero_copy): as
+// launch_merkle_pieces, but piece i is read at the device-visible address
+// srcs[i] (HBM, or a registered host buffer's mapping; 16-byte aligned; may be
+// 0 when lens[i] == 0) with cooperative loads.  work as merkle_pieces_work says.
+// merkle_zc_geometry: leaves per workgroup, leaves per wave, bytes per leaf
+// per tile, tiles in flight per wave (host-only).
+hipError_t launch_merkle_zc_pieces(const uint64_t* srcs, const uint32_t* lens, const uint8_t* log2w, uint32_t n,
+                                   uint32_t log2_width, uint8_t* work, uint8_t* roots, const uint8_t* expected,
+                                   uint8_t* matched, hipStream_t stream);
+void merkle_zc_geometry(uint32_t out[4]);
 // The block check (vx_merkle_device_block_check): the ragged batch's leaves
 // against row g of expected_leaves, one bit per block into bad (uint64 words,
 // max(1, 2^log2_width / 64) per piece, every word written) and / or the leaf

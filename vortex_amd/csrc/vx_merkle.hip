@@ -380,6 +380,49 @@ int vx_tuning_zero_leaf_kernel(const uint32_t* d_rows, const uint32_t* d_lens, u
     return e == hipSuccess ? 0 : hip_fail(e, "vx_tuning_zero_leaf_kernel");
 }
 
+void vx_tuning_merkle_zc_geometry(uint32_t* out) {
+    if (out) vx::merkle_zc_geometry(out);
+}
+
+// The launch and, above 256 leaves, the node pass, and nothing else.  The tile
+// tops are one process-wide device block, grown on demand and kept: a call
+// that grows it waits for the device first, so calls on different streams must
+// not overlap at widths above 8.
+int vx_tuning_merkle_zc_kernel(const uint64_t* d_srcs, const uint32_t* d_lens, const uint8_t* d_log2w, uint32_t n,
+                               uint32_t log2_width, void* d_roots, const void* d_expected, void* d_matched,
+                               void* stream) {
+    if (n == 0) return 0;
+    if (!d_srcs || !d_lens) return fail(VX_EINVAL, "vx_tuning_merkle_zc_kernel: NULL d_srcs or d_lens");
+    if ((reinterpret_cast<uintptr_t>(d_srcs) & 7) || (reinterpret_cast<uintptr_t>(d_lens) & 3))
+        return fail(VX_EINVAL, "vx_tuning_merkle_zc_kernel: d_srcs must be 8-byte and d_lens 4-byte aligned");
+    if (log2_width > VX_MERKLE_MAX_LOG2_WIDTH) return fail(VX_EINVAL, "vx_tuning_merkle_zc_kernel: log2_width > 17");
+    if (((uint64_t)n << log2_width) >> 31)
+        return fail(VX_EINVAL, "vx_tuning_merkle_zc_kernel: n << log2_width does not fit 31 bits");
+    if ((reinterpret_cast<uintptr_t>(d_roots) & 15) || (reinterpret_cast<uintptr_t>(d_expected) & 3))
+        return fail(VX_EINVAL, "vx_tuning_merkle_zc_kernel: d_roots must be 16-byte and d_expected 4-byte aligned");
+    static std::mutex mu;
+    static uint8_t* tops = nullptr;
+    static uint64_t tops_cap = 0;
+    std::lock_guard<std::mutex> lock(mu);
+    const uint64_t need = vx::merkle_pieces_work(n, log2_width);
+    if (need > tops_cap) {
+        hipError_t e = hipDeviceSynchronize();  // nothing enqueued earlier still writes the old block
+        if (e == hipSuccess && tops) e = hipFree(tops);
+        tops = nullptr;
+        tops_cap = 0;
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&tops), need);
+        if (e != hipSuccess) return hip_fail(e, "vx_tuning_merkle_zc_kernel: tile tops allocation");
+        tops_cap = need;
+    }
+    const bool verdict = d_expected && d_matched;
+    hipError_t e = vx::launch_merkle_zc_pieces(d_srcs, d_lens, d_log2w, n, log2_width, tops,
+                                               static_cast<uint8_t*>(d_roots),
+                                               verdict ? static_cast<const uint8_t*>(d_expected) : nullptr,
+                                               verdict ? static_cast<uint8_t*>(d_matched) : nullptr,
+                                               static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : hip_fail(e, "vx_tuning_merkle_zc_kernel");
+}
+
 // ---- `piece layers` and hash proofs in batches ----
 
 int vx_merkle_layers_plan(const uint32_t* counts, uint32_t n_layers, struct vx_merkle_layers_plan* plan,

@@ -229,31 +229,55 @@ static int launch_v1(vx_ctx* c, int si) {
     return mark_inflight(c, s);
 }
 
-// As launch_v1, never zero-copy: a v2 slot has no chain for the transfer to
-// hide behind, so gather-then-hash loses only the hash of one leaf (DESIGN.md
-// §3.7).  The fused piece kernel runs at the slot's widest tree; above 256
-// leaves it leaves tile tops in d_tops and the node kernel follows
-// (launch_merkle_pieces).
+// As launch_v1, not zero-copy unless vx_set_merkle_zero_copy: a v2 slot has no
+// chain for the transfer to hide behind, so gather-then-hash loses only the
+// hash of one leaf.  The fused piece kernel runs at the
+// slot's widest tree; above 256 leaves it leaves tile tops in d_tops and the
+// node kernel follows (launch_merkle_pieces).  With the setting on, a slot
+// that qualifies as a v1 slot does (every piece registered and 16-byte
+// aligned: nothing staged, no runs) is hashed by the zero-copy piece kernel
+// through the pieces' device mappings: only the lens, srcs, log2w and expected
+// tables go ahead of it, and nothing waits for the copy chain.
 static int launch_v2(vx_ctx* c, int si) {
     Slot& s = c->slots[si];
     Slot::V2& v = s.v2;
     hipStream_t cs = s.stream;
     const uint32_t n = s.n, K = v.kmax;
-    if (int rc = copy_pieces(c, si, true)) return rc;
+    const bool zc = c->merkle_zc && s.gtiles && s.all_mapped;
+    if (zc) {
+        VX_HIP(hipMemcpyAsync(s.d_lens, s.h_lens, (size_t)n * 4, hipMemcpyHostToDevice, cs));
+        VX_HIP(hipMemcpyAsync(s.d_src, s.h_src, (size_t)n * 8, hipMemcpyHostToDevice, cs));
+    } else if (int rc = copy_pieces(c, si, true)) {
+        return rc;
+    }
     VX_HIP(hipMemcpyAsync(v.d_log2w, v.h_log2w, n, hipMemcpyHostToDevice, cs));
     if (s.has_expected) VX_HIP(hipMemcpyAsync(v.d_exp32, v.h_exp32, (size_t)n * 32, hipMemcpyHostToDevice, cs));
     VX_HIP(hipEventRecord(s.copied, cs));
     mark_launched(c, si);
     uint8_t *d_exp = s.has_expected ? v.d_exp32 : nullptr, *d_matched = s.has_expected ? s.d_matched : nullptr;
+    hipError_t e;
+    if (zc) {
+        if (!v.d_tops.reserve(vx::merkle_pieces_work(n, K))) return fail(VX_ENOMEM, "v2 tile tops allocation failed");
+        e = vx::launch_merkle_zc_pieces(s.d_src, s.d_lens, v.d_log2w, n, K, v.d_tops.get(), v.d_roots, d_exp, d_matched,
+                                        cs);
+        // vx_get_stats is the same with the setting on or off: the slot's tiles cross PCIe once either
+        // way and count as pulled from registered memory; which kernel pulled them is the trace's
+        c->stats.gather_tiles += s.gtiles;
+        c->merkle_zc_trace.slots++;
+        c->merkle_zc_trace.pieces += n;
+        for (uint32_t i = 0; i < n; ++i) c->merkle_zc_trace.bytes += s.h_lens[i];
+    } else {
+        c->merkle_zc_trace.fallback_slots += c->merkle_zc != 0;
 #if VX_MERKLE_ASYNC_FUSED
-    if (!v.d_tops.reserve(vx::merkle_pieces_work(n, K))) return fail(VX_ENOMEM, "v2 tile tops allocation failed");
-    hipError_t e = vx::launch_merkle_pieces(s.d_arena.get(), s.d_offsets, s.d_lens, v.d_log2w, n, K, v.d_tops.get(), v.d_roots,
-                                            d_exp, d_matched, cs);
+        if (!v.d_tops.reserve(vx::merkle_pieces_work(n, K))) return fail(VX_ENOMEM, "v2 tile tops allocation failed");
+        e = vx::launch_merkle_pieces(s.d_arena.get(), s.d_offsets, s.d_lens, v.d_log2w, n, K, v.d_tops.get(), v.d_roots,
+                                     d_exp, d_matched, cs);
 #else  // the A/B leg (vx_tuning.h): the leaf + node pair, d_tops its leaf array
-    if (!v.d_tops.reserve(((uint64_t)n << K) * 32)) return fail(VX_ENOMEM, "v2 tile tops allocation failed");
-    hipError_t e = vx::launch_merkle_ragged(s.d_arena.get(), s.d_offsets, s.d_lens, v.d_log2w, n, K, v.d_tops.get(), v.d_roots,
-                                            d_exp, d_matched, cs);
+        if (!v.d_tops.reserve(((uint64_t)n << K) * 32)) return fail(VX_ENOMEM, "v2 tile tops allocation failed");
+        e = vx::launch_merkle_ragged(s.d_arena.get(), s.d_offsets, s.d_lens, v.d_log2w, n, K, v.d_tops.get(), v.d_roots,
+                                     d_exp, d_matched, cs);
 #endif
+    }
     if (e != hipSuccess) return hip_fail(e, "merkle piece kernel launch");
     VX_HIP(hipMemcpyAsync(v.h_roots, v.d_roots, (size_t)n * 32, hipMemcpyDeviceToHost, cs));
     return mark_inflight(c, s);
@@ -769,6 +793,18 @@ int vx_merkle_submit(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len,
     if (!c) return fail(VX_EINVAL, "vx_merkle_submit: NULL context");
     return checked_submit(c, "vx_merkle_submit",
                           {.kind = Kind::V2, .tag = tag, .data = data, .len = len, .expected = expected, .log2w = log2w});
+}
+
+int vx_set_merkle_zero_copy(vx_ctx* c, int on) {
+    if (!c || (on != 0 && on != 1)) return fail(VX_EINVAL, "vx_set_merkle_zero_copy: NULL context, or on not 0/1");
+    c->merkle_zc = on;
+    return 0;
+}
+
+int vx_merkle_zero_copy_trace(const vx_ctx* c, vx_merkle_zc_trace* out) {
+    if (!c || !out) return fail(VX_EINVAL, "vx_merkle_zero_copy_trace: NULL argument");
+    *out = c->merkle_zc_trace;
+    return 0;
 }
 
 int vx_hybrid_submit(vx_ctx* c, uint64_t tag, const uint8_t* data, uint32_t len, uint32_t pad_len, uint32_t log2w,

@@ -157,6 +157,7 @@ class HashPool:
         self._registered: dict[int, tuple[int, Any, Any]] = {}  # id(buf) -> (address, keep-alive, buf)
         self._hybrid_rows = 0  # rows of the tables given to set_hybrid_tables
         self._skip_holes = False  # vx_set_skip_holes' default
+        self._merkle_zero_copy = False  # vx_set_merkle_zero_copy's default
 
     # -- lifecycle ---------------------------------------------------------
     def close(self) -> None:
@@ -498,6 +499,28 @@ class HashPool:
         t = _lib.vx_hole_trace()
         check(self.lib.vx_last_verify_holes(self._h, ctypes.byref(t)), "vx_last_verify_holes", self.lib)
         return {name: getattr(t, name) for name, _ in _lib.vx_hole_trace._fields_}
+
+    @property
+    def merkle_zero_copy(self) -> bool:
+        """Whether spawn_merkle's slots of registered, 16-byte aligned pieces
+        are hashed straight out of host memory (vx_set_merkle_zero_copy,
+        DESIGN.md §6.5).  Off by default; read when a slot is launched, so it
+        may change while pieces are pending.  Results and stats() are the same
+        either way; merkle_zero_copy_trace() says what it did."""
+        return self._merkle_zero_copy
+
+    @merkle_zero_copy.setter
+    def merkle_zero_copy(self, on: bool) -> None:
+        check(self.lib.vx_set_merkle_zero_copy(self._h, 1 if on else 0), "vx_set_merkle_zero_copy", self.lib)
+        self._merkle_zero_copy = bool(on)
+
+    def merkle_zero_copy_trace(self) -> dict:
+        """Since the pool was made (vx_merkle_zero_copy_trace): v2 slots
+        launched zero-copy, their pieces and bytes, and fallback_slots, the v2
+        slots that took the gathered path while the setting was on."""
+        t = _lib.merkle_zc_trace_type()()
+        check(self.lib.vx_merkle_zero_copy_trace(self._h, ctypes.byref(t)), "vx_merkle_zero_copy_trace", self.lib)
+        return {name: getattr(t, name) for name in _lib.MERKLE_ZC_TRACE_FIELDS}
 
     def last_verify_rounds(self) -> list[dict]:
         """The last verify_files call's round timeline (vx_last_verify_rounds):
